@@ -5,8 +5,14 @@ N=1 (default): BASELINE.json configs[1] — bloom-1b1 as one stage on one GPU, b
 decode steps.  One "step" = one decode token for every row of the batch through the whole
 model.  N>1 (one rank per GPU: under torchrun, or `bench.py --gpus N` starts the N ranks
 itself): the same model split into N stages by the server's round-robin layer assignment
-(server.py:893-905), activations over RCCL send/recv, 2N micro-batches in flight, plus the
-configs[3] / configs[4] records — see distributed_inference_demo_amd/pipeline_bench.py.
+(server.py:893-905), activations over RCCL send/recv, 2N micro-batches in flight — see
+distributed_inference_demo_amd/pipeline_bench.py.
+
+A plain run does only what the headline figure needs: set up (one prefill), warm up, time the K
+steps, write the outputs if --dump-outputs is given, print the line.  Everything else the benchmark
+measures runs only with --full: the timed prefill and its GEMM split, the decode-GEMV roofline and its
+PMC traffic passes, the measured HBM / MFMA rates, the pipeline code's N = 1 point with the configs
+records, the host-CPU baseline, and at N > 1 the strong / configs[2..4] / replicas records.
 
 Prints ONE JSON line (rank 0).  Inputs are resident in HBM before the timed region.
 """
@@ -21,6 +27,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E vendor peak (MI355X_MICROARCH.md)
 BF16_PEAK_TFLOPS = 2500.0   # dense bf16 MFMA vendor peak
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: all files of one dump together
 
 
 def parse(argv=None):
@@ -35,6 +42,14 @@ def parse(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--weights", default="bf16", choices=["bf16", "int8"],
                    help="int8: weight-only int8 block matrices (BS_FLAG_INT8_WEIGHTS, the bloom*-int8 variants)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement (prefill timing, roofline + PMC traffic, HBM / MFMA "
+                        "probes, pipeline_n1 + configs records, strong / replicas records, CPU baseline); the "
+                        "--no-* options and --cpu-baseline select among them and mean nothing without it")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step returned to its caller as "
+                        "DIR/<name>.npy: `tokens` [rows] (float64), and at N = 1 `next_step_logits` [rows][vocab] "
+                        "(float32) of one more, untimed, step from the same state")
     p.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU checker on a bounded sample")
     p.add_argument("--cpu-steps", type=int, default=24)
     p.add_argument("--no-profile", action="store_true")
@@ -63,7 +78,27 @@ def parse(argv=None):
     p.add_argument("--executor", default=None,
                    help="pipeline: module:function returning the per-stage executor factory for (model, dtype, "
                         "seed) -- a test hook for the gloo backend (tests/bench_checker.py)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if not args.full:  # a plain run: the headline figure only
+        args.cpu_baseline = 0
+        args.no_profile = args.no_pmc = args.no_pipeline_n1 = True
+        args.no_strong = args.no_configs = args.no_replicas = True
+    return args
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per array under `path`, float32 arrays as they are and everything else
+    (token ids) as float64.  An array over DUMP_MAX_BYTES / len(arrays) is cut to a fixed seeded sample of
+    its flattened elements (the same indices in every run), so a dump stays under DUMP_MAX_BYTES."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        keep = DUMP_MAX_BYTES // len(arrays) // a.itemsize
+        if a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def pmc_traffic(args, kernel_tag, timeout=240):
@@ -82,7 +117,7 @@ def pmc_traffic(args, kernel_tag, timeout=240):
     tot = {}
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         cmd = [prof, "--pmc", counter, "-d", out, "-o", counter.lower(), "--output-format", "csv", "--",
-               sys.executable, os.path.abspath(__file__), "--steps", "8", "--warmup", "2", "--cpu-baseline", "0",
+               sys.executable, os.path.abspath(__file__), "--full", "--steps", "8", "--warmup", "2", "--cpu-baseline", "0",
                "--no-profile", "--no-pmc", "--no-pipeline-n1", "--model", args.model, "--batch", str(args.batch), "--prompt",
                str(args.prompt), "--dtype", args.dtype, "--seed", str(args.seed),
                "--weights", args.weights]
@@ -271,15 +306,17 @@ def bench_single(args):
         stream = cs.cuda_stream
         ids = torch.from_numpy(_prompt(B, P, m.vocab)).to(dev)
         tok = torch.empty(B, dtype=torch.int32, device=dev)
-        # prefill: one untimed pass (first launch of every kernel), the timed pass (bracketed by syncs,
-        # no events), then a pass with HIP events around every GEMM for the GEMM/other split.  Every pass
-        # rewrites the same KV rows of slot 0 with the same values.
+        # prefill: one untimed pass (first launch of every kernel) and, with --full, the timed pass (bracketed
+        # by syncs, no events), then a pass with HIP events around every GEMM for the GEMM/other split.  Every
+        # pass rewrites the same KV rows of slot 0 with the same values.
         st.forward(ids, tok, B, P, slot=0, past_len=0, stream=stream)
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        st.forward(ids, tok, B, P, slot=0, past_len=0, stream=stream)
-        torch.cuda.synchronize()
-        t_prefill = time.perf_counter() - t0
+        t_prefill = None
+        if args.full:
+            t0 = time.perf_counter()
+            st.forward(ids, tok, B, P, slot=0, past_len=0, stream=stream)
+            torch.cuda.synchronize()
+            t_prefill = time.perf_counter() - t0
         pf_ms = pf_n = pf_flops = 0
         if not args.no_profile:
             st.profile_enable(2)
@@ -298,6 +335,15 @@ def bench_single(args):
             past += 1
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            # the last timed step's tokens, and the logits of one more step from the same state: it writes the
+            # KV row at `past` without advancing it (the roofline pass below rewrites that row with the same values)
+            nxt = torch.empty_like(tok)
+            lg = torch.empty(B, m.vocab, dtype=torch.float32, device=dev)
+            st.forward(tok, nxt, B, 1, slot=0, past_len=past, logits=lg, stream=stream)
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, {"tokens": tok.cpu().numpy(), "next_step_logits": lg.cpu().numpy()})
+            del nxt, lg
         # roofline pass: the same decode steps, HIP events around every weight GEMV (class 1, eager)
         g_ms = g_n = g_bytes = 0
         if prof_steps:
@@ -349,6 +395,9 @@ def bench_single(args):
                                        "behind a 3 ms stream spin (no host-submission gaps)"}
     res["stage_hbm"] = {"algo_bytes_per_step": step_bytes, "achieved_GBps": step_bytes / (ms_step * 1e-3) / 1e9,
                         "frac_of_peak": step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+    if not args.full:
+        st.close()
+        return res
     res["prefill"] = {"tokens": B * P, "ms": t_prefill * 1e3, "tokens_per_s": B * P / t_prefill,
                       "algo_flops": config.prefill_flops(m, m.n_layer, B, P, True),
                       "timing": "second of three identical prefills (the first warms every kernel), host clock "
@@ -439,7 +488,8 @@ def main(argv=None):
             # the N = 1 point of the pipeline curve and its configs records ride on the headline: a failure there
             # (out of memory on a shared GPU, a 7b1-shape error) is reported in the line, never loses it
             try:
-                p1, _, _ = _pipeline(args)
+                # (--dump-outputs holds the headline run's outputs: the ride-along writes none)
+                p1, _, _ = _pipeline(argparse.Namespace(**dict(vars(args), dump_outputs=None)))
                 res["pipeline_n1"] = {k: p1[k] for k in ("value", "ms_per_step", "config", "weak_definition",
                                                          "scaling_ref", "stage_hbm", "prefill", "strong", "configs2",
                                                          "configs3", "configs4", "replicas") if k in p1}

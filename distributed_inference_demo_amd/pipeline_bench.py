@@ -80,7 +80,7 @@ def _progress(msg):
 
 
 def run_pipeline(model, rank, world, dev, *, mb_rows, n_mb, head_split, prompts, steps, warmup, dtype="bf16",
-                 seed=0, prof_rounds=0, executor_factory=None, replica=False):
+                 seed=0, prof_rounds=0, executor_factory=None, replica=False, last_tokens=None):
     """Build this rank's stage + Pipeline once, then for each prompt length P in `prompts`: a timed P-token
     prefill round (every micro-batch streams through the stages; per-stage forward times), `warmup` and
     `steps` timed decode rounds (barrier + sync on both sides, max over ranks).  After the first point,
@@ -88,7 +88,9 @@ def run_pipeline(model, rank, world, dev, *, mb_rows, n_mb, head_split, prompts,
     roofline).  Rank 0 returns [one record per P], other ranks None.
     replica=True: every rank builds the WHOLE model as one stage on its own GPU (a world-1 pipeline, no
     communication on the data path) and runs n_mb x mb_rows rows of its own; the timing brackets (barrier +
-    sync, max over ranks) are the same, and the record's value counts the rows of all ranks."""
+    sync, max over ranks) are the same, and the record's value counts the rows of all ranks.
+    last_tokens (a list): rank 0 appends, per prompt length, the tokens the last timed round returned to it
+    (int32 [n_mb * mb_rows] on the host) -- bench.py's --dump-outputs."""
     W, K = warmup, steps
     pmax = max(prompts)
     b_rank, b_world = (0, 1) if replica else (rank, world)
@@ -129,6 +131,8 @@ def run_pipeline(model, rank, world, dev, *, mb_rows, n_mb, head_split, prompts,
         _sync(dev)
         dist.barrier()
         dt = _max_over_ranks(time.perf_counter() - t0, dev)
+        if last_tokens is not None and pipe.is_first:
+            last_tokens.append(torch.cat(pipe.tok).cpu().numpy())
         g = None
         if i == 0 and st is not None and prof_rounds:
             st.profile_enable(1)
@@ -248,8 +252,14 @@ def bench_pipeline(args, backend="nccl", executor_factory=None):
 
     n_mb = 2 * world
     common = dict(head_split=head_split, steps=args.steps, warmup=args.warmup, dtype=dtype, seed=seed)
+    dump, toks = getattr(args, "dump_outputs", None), []
     (weak,) = run_pipeline(model, rank, world, dev, mb_rows=args.batch, n_mb=n_mb, prompts=[args.prompt],
-                           prof_rounds=prof_rounds, executor_factory=factory(model), **common) or [None]
+                           prof_rounds=prof_rounds, executor_factory=factory(model),
+                           last_tokens=toks if dump else None, **common) or [None]
+    if dump and toks:  # rank 0: what the last timed round of the line's own (weak) workload returned
+        import numpy as np
+        os.makedirs(dump, exist_ok=True)
+        np.save(os.path.join(dump, "tokens.npy"), toks[0].astype(np.float64))
     strong = None
     if not getattr(args, "no_strong", False):
         want = 16 * args.batch

@@ -18,7 +18,9 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
+sys.path.insert(0, os.path.join(HERE, ".."))
 from oracle import gen_np  # noqa: E402
+from golden_io import save_parts  # noqa: E402
 
 from transformers import BloomConfig, BloomForCausalLM, BloomForSequenceClassification  # noqa: E402
 from transformers.models.bloom.modeling_bloom import build_alibi_tensor  # noqa: E402
@@ -113,7 +115,7 @@ def family_blocks():
         out[f"{name}_out7"] = l7[0]
         out[f"{name}_out1"] = l1[0]
         print("family", name, "ok")
-    np.savez_compressed(os.path.join(HERE, "family_blocks.npz"), **out)
+    save_parts("family_blocks", out)  # family_blocks_NN.npz: 2.5 MB in one file, and no committed file exceeds 1 MiB
 
 
 def tiny_classify():

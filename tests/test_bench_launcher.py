@@ -11,6 +11,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,9 +19,10 @@ ARGS = ["--backend", "gloo", "--model", "tiny", "--configs-model", "tiny", "--pr
         "--warmup", "1", "--configs3-mb", "3", "--configs3-prompt", "5", "--configs4-rows", "4",
         "--configs4-ctx", "4,12,16", "--configs2-model", "tiny", "--configs2-prompt", "5", "--configs2-steps", "2",
         "--cpu-baseline", "0", "--no-profile", "--dtype", "fp32"]
+FULL = ["--full"]  # the strong / configs / replicas records ride only on a --full run
 
 
-def _bench(n, executor="bench_checker:make", extra=()):
+def _bench(n, executor="bench_checker:make", extra=FULL):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]), OMP_NUM_THREADS="1")
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--executor", executor]
@@ -67,8 +69,27 @@ def test_bench_gpus_n_starts_n_ranks(n):
     assert sr["weak_value"] == res["value"]
 
 
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_tokens(tmp_path):
+    """Without --full: the weak line alone (no strong / configs / replicas / CPU baseline records), K timed rounds, and
+    --dump-outputs writes the last round's tokens of every row, the same from run to run."""
+    outs = []
+    for d in ("a", "b"):
+        r = _bench(2, extra=["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        assert res["n_gpus"] == 2 and res["steps"] == 3 and res["value"] > 0 and res["ms_per_step"] > 0
+        assert res["value"] == pytest.approx(res["config"]["batch"] * 1e3 / res["ms_per_step"])
+        assert not {"strong", "configs2", "configs3", "configs4", "replicas", "cpu_baseline"} & set(res)
+        assert sorted(os.listdir(tmp_path / d)) == ["tokens.npy"]
+        outs.append(np.load(tmp_path / d / "tokens.npy"))
+    assert outs[0].dtype == np.float64 and outs[0].shape == (4,) and (outs[0] == outs[1]).all()
+    assert ((0 <= outs[0]) & (outs[0] < 512) & (outs[0] == np.floor(outs[0]))).all()
+
+
 def test_bench_rank_failure_is_nonzero():
-    r = _bench(2, executor="bench_checker:make_failing", extra=["--no-strong", "--no-configs"])
+    r = _bench(2, executor="bench_checker:make_failing", extra=["--full", "--no-strong", "--no-configs"])
     assert r.returncode != 0
 
 

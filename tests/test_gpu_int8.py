@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from distributed_inference_demo_amd.stage import Stage
+from golden_io import load_parts
 from oracle import gen_np
 from oracle.oracle import OracleStage
 
@@ -63,7 +64,7 @@ def test_int8_family_block_prefill_and_decode(fam):
     """One block at each family's real width: S=64 prefill (dequantized operand + bf16 GEMM), S=7
     after 15 cached (int8 GEMV, 7 rows), S=1 after 22 cached (int8 GEMV, 1 row)."""
     import os
-    f = np.load(os.path.join(os.path.dirname(__file__), "golden", "family_blocks.npz"))
+    f = load_parts("family_blocks")
     h, nh, _, V, seed = (int(v) for v in f[fam + "_config"])
     gs, os_ = pair8(h, nh, 1, V, 0, 1, seed, max_ctx=64, max_tokens=64, is_last=False)
     check_close(gs.forward_host(f[fam + "_ids64"], 1, 64), os_.forward(f[fam + "_ids64"], 1, 64), "bf16",

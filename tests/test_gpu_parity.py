@@ -25,6 +25,7 @@ from distributed_inference_demo_amd.stage import (BloomStageError, Stage, create
                                                   run_inference_master_residual, run_inference_worker_residual,
                                                   run_inference_worker_residual_last_generation)
 from distributed_inference_demo_amd.config import BloomDims
+from golden_io import load_parts
 from oracle import gen_np
 from oracle.oracle import EMUL_DEVICE, OracleStage
 
@@ -180,7 +181,7 @@ def test_tiny_stage_splits_match_oracle(dtype):
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("fam", ["560m", "1b1", "3b", "7b1"])
 def test_family_block_prefill_and_decode(fam, dtype):
-    f = np.load(os.path.join(G, "family_blocks.npz"))
+    f = load_parts("family_blocks")
     h, nh, _, V, seed = (int(v) for v in f[fam + "_config"])
     gs, os_ = pair(h, nh, 1, V, 0, 1, dtype, seed, max_ctx=64, max_tokens=64, is_last=False)
     out_g = gs.forward_host(f[fam + "_ids64"], 1, 64)

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+from golden_io import load_parts
 from oracle import gen_np
 from oracle.oracle import OracleStage, alibi_slopes, gen_tensor, prompt_ids
 
@@ -84,7 +85,7 @@ def test_nonpow2_heads_match_hf():
 
 @pytest.mark.parametrize("fam", ["560m", "1b1", "3b", "7b1"])
 def test_family_block_matches_hf(fam):
-    f = _load("family_blocks.npz")
+    f = load_parts("family_blocks")
     h, nh, _, V, seed = (int(v) for v in f[fam + "_config"])
     st = OracleStage(h, nh, 1, V, 0, 1, max_batch=1, max_ctx=64, seed=seed, is_last=False)
     ref = f[fam + "_out64"]
@@ -110,7 +111,7 @@ def test_bf16_noise_floor_of_the_checker():
     """Two fp32 accumulation orders of the same bf16-emulated block: the spread the GPU-vs-oracle
     bf16 tolerance must admit (see tests/test_gpu_parity.py header)."""
     from oracle.oracle import lib
-    f = _load("family_blocks.npz")
+    f = load_parts("family_blocks")
     h, nh, _, V, seed = (int(v) for v in f["7b1_config"])
     outs = []
     try:

@@ -6,8 +6,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: F401
 from distributed_inference_demo_amd.stage import Stage
 from oracle.oracle import OracleStage, lib as olib
-G = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "family_blocks.npz")
-f = np.load(G)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from golden_io import load_parts
+f = load_parts("family_blocks")
 for fam in ["560m", "1b1", "3b", "7b1"]:
     h, nh, _, V, seed = (int(v) for v in f[fam + "_config"])
     res = {}

@@ -17,8 +17,10 @@ import torch  # noqa: F401,E402
 from distributed_inference_demo_amd.stage import Stage  # noqa: E402
 from oracle.oracle import OracleStage  # noqa: E402
 
-G = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "family_blocks.npz")
-f = np.load(G)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from golden_io import load_parts  # noqa: E402
+
+f = load_parts("family_blocks")
 
 
 def rep(name, got, ref):
