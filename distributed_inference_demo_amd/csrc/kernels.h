@@ -126,6 +126,30 @@ void launch_linear_parts(const AttnParts& p, const void* W, int M, int N, int K,
 void launch_argmax_finalize(const unsigned long long* keys, int M, int ntiles, const unsigned long long* keys_in,
                             unsigned long long* keys_out, int* tokens, hipStream_t s, int* past_adv = nullptr,
                             int seq = 0);
+// ---- Greedy lm_head screening (bf16 stages, M <= 2, K <= 4096; kernels.hip "Greedy lm_head screening") ----
+// The int8 shadow copy of the tied embedding with its per-row bound constants (made once at stage init) and the
+// per-step buffers of the screened tail; ntiles = V / 16.
+struct HeadScreen {
+  const int8_t* Q;     // [V][K], launch_quantize_rows of the bf16 embedding
+  const float* scale;  // [V]
+  const float* cb;     // [V] launch_head_bound: |exact logit - int8 logit| <= ||x~|| * cb[n]
+  float* hilo;         // [M][ntiles][2]: max(s^ + E), max(s^ - E) of each 16-row tile
+  float* rnorm;        // [M] inflated ||x~_m||
+  float* lstar;        // [M] max over tiles of lo
+  int* list;           // [M][ntiles] candidate tiles (unordered)
+  int* count;          // [M]
+};
+bool head_screen_supported(int M, int K);
+// cb[n] >= ||w_n - scale_n Q_n||_2 + 2^-10 (||w_n||_2 + ||scale_n Q_n||_2), rounded up (fp64 sums).
+void launch_head_bound(const void* W_bf16, const int8_t* Q, const float* scale, float* cb, int N, int K, hipStream_t s);
+// (a) ln_f of rows x[m * row_stride + row_offset] + the int8 pass over Qh -> hilo, rnorm.  cus: CUs of the device.
+void launch_head_screen(const HeadScreen& hs, const float* x, int row_stride, int row_offset, const void* gamma,
+                        const void* beta, float eps, int M, int V, int K, int cus, hipStream_t s);
+// (b) select the candidate tiles, (c) re-score them with the exact head's block body (ep: the EPI_ARGMAX epilogue
+// of the full head, logits null), (d) reduce the listed keys -> tokens[m]; past_adv[m] += seq (the step's last kernel).
+void launch_head_pick(const HeadScreen& hs, const float* x, int row_stride, int row_offset, const void* gamma,
+                      const void* beta, float eps, const void* W, int M, int V, int K, const Epi& ep, int cus,
+                      int* tokens, int* past_adv, int seq, hipStream_t s);
 // Sequence-classification head: xn (T) [M][K] . score (T) [n_labels][K] -> logits fp32 [M][n_labels] (optional),
 // cls[m] = first maximal label (inference.cpp:57-69); past_adv[m] += seq (optional).  n_labels <= 64, K % 8 == 0.
 void launch_classify(int is_bf16, const void* xn, const void* score, int M, int n_labels, int K, float* logits,

@@ -933,7 +933,7 @@ __device__ __forceinline__ void gemv_rows_block(const bf16* __restrict__ W, cons
       __syncthreads();
       if (threadIdx.x < 64) {
         const int col = threadIdx.x & 15, m = threadIdx.x >> 4;  // 4 rows of 16 lanes: m < 4
-        const int n = blockIdx.x * 16 + col;
+        const int n = bid * 16 + col;  // bid: blockIdx.x in gemv_rows_kernel, a listed tile in head_rescore_kernel
         const float v = m < MM ? tv[col * MM + (m < MM ? m : 0)] : 0.f;
         argmax_tile16(ep, m, n, v, m < M && n < N, (N + 15) >> 4);
       }
@@ -3526,4 +3526,337 @@ void launch_linear_q8(const void* X, const int8_t* Q, const float* scale, void* 
   // prefill: dequantize to the bf16 scratch, then the bf16 GEMM
   launch_dequant_rows(Q, nullptr, w_scratch, N, K, s);
   launch_linear(1, X, w_scratch, M, N, K, e, s);
+}
+
+// ------------------------------------------------------------------------------------
+// Greedy lm_head screening ("Head screening").  A greedy step needs one token id per row, not
+// 250 880 logits: an int8 shadow copy Qh of the tied embedding (quantize_rows_kernel's rule, made once at stage init)
+// is streamed instead of the bf16 rows -- half the bytes -- and yields for every vocabulary row n an approximate logit
+// s^ = scale[n] * sum_k Qh[n][k] * x~[k] with a rigorous error radius E against the logit l^ the exact head computes:
+//   |l^ - s^| <= |l^ - x~.w| + |x~.(w - scale Q)| + |x~.(scale Q) - s^|
+//            <= ||x~|| * (||w - scale Q|| + rho * (||w|| + ||scale Q||)) = ||x~|| * c[n]            (Cauchy-Schwarz)
+// rho covers the fp32 accumulation of both dot products in any order: a K-term fp32 sum of products is off by at most
+// gamma * ||a|| ||b||, gamma ~ 2 K 2^-24 (two roundings per product pair of v_dot2_f32_bf16, one per FMA of the
+// screen); the X_LN head has K <= 4096, so gamma <= 2^-11 and rho = 2^-10 is generous.
+// Per 16-row tile (the exact head's tiling) the screen stores hi = max(s^ + E), lo = max(s^ - E).  The winner n* has
+// s^ + E >= l^(n*) >= max_n l^(n) >= max_n (s^(n) - E(n)) = L*, so its tile -- and the tile of every row tied with it
+// -- has hi >= L*: head_select lists those tiles, head_rescore runs the exact head's block body on them
+// (bit-identical keys), head_screen_finalize reduces the listed keys.  No kernel waits on another block.
+// ------------------------------------------------------------------------------------
+constexpr float kHsRho = 0x1p-10f;
+
+// c[n] >= ||w_n - scale_n Q_n|| + rho (||w_n|| + ||scale_n Q_n||): fp64 sums (w, scale and scale * Q are exact in
+// fp64; the K <= 4096 term sums and the roots are off by < 2^-40 relative), inflated by 2^-30 and rounded UP to fp32.
+__global__ __launch_bounds__(256) void head_bound_kernel(const bf16* __restrict__ W, const int8_t* __restrict__ Q,
+                                                         const float* __restrict__ scale, float* __restrict__ c, int K) {
+  const size_t row = blockIdx.x;
+  const double sc = (double)scale[row];
+  double d2 = 0.0, w2 = 0.0, q2 = 0.0;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const double w = (double)(float)W[row * K + k], q = sc * (double)Q[row * K + k], d = w - q;
+    d2 += d * d; w2 += w * w; q2 += q * q;
+  }
+  __shared__ double red[3][256];
+  red[0][threadIdx.x] = d2; red[1][threadIdx.x] = w2; red[2][threadIdx.x] = q2;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o)
+      for (int j = 0; j < 3; j++) red[j][threadIdx.x] += red[j][threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double b = (sqrt(red[0][0]) + (double)kHsRho * (sqrt(red[1][0]) + sqrt(red[2][0]))) * (1.0 + 0x1p-30);
+    float f = (float)b;
+    if (!((double)f >= b)) f = nextafterf(f, INFINITY);  // round up; a NaN bound stays NaN (the screen then lists all)
+    c[row] = f;
+  }
+}
+
+void launch_head_bound(const void* W_bf16, const int8_t* Q, const float* scale, float* c, int N, int K, hipStream_t s) {
+  if (N > 0) head_bound_kernel<<<N, 256, 0, s>>>((const bf16*)W_bf16, Q, scale, c, K);
+}
+
+// (a) Screen.  One 16-wave block per CU; block b owns the contiguous tiles [b T / G, (b + 1) T / G) -- equal bytes per
+// CU to within one tile -- and its waves take them round robin.  ln_f runs in the prologue exactly as in the exact
+// head (ln_rows_load / ln_rows_finish: the same bf16 row x~ in LDS).  A wave walks its tiles in units of R rows x U
+// 512-column chunks (8 int8 weights = 8 B per lane and chunk, non-temporal; the lane's columns are the exact head's),
+// the next two units' loads in flight while this one is computed.  The weights convert exactly (u = q ^ 0x80 through
+// v_cvt_f32_ubyte*, minus 128) and accumulate with fp32 FMAs: |s^ - x~.(scale Q)| is inside rho's budget (no
+// offset-form cancellation).  hi / lo are pushed outwards by 2^-22 relative, so the roundings of s^ + E and s^ - E
+// cannot pull them inside; a non-finite s^ or E stores hi = +inf, which makes head_select list every tile.
+template <int MM, int U, int R>
+__global__ __launch_bounds__(1024) void gemv_head_screen_kernel(const int8_t* __restrict__ Q, const float* __restrict__ scale,
+                                                           const float* __restrict__ cb, LnArgs ln, int M, int ntiles,
+                                                           int K, float2* __restrict__ hilo, float* __restrict__ rnorm) {
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* scratch = reinterpret_cast<float*>(smem);  // 64 floats
+  bf16* xs = reinterpret_cast<bf16*>(smem + 256);    // [M][K]
+  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t0 = (int)((long long)blockIdx.x * ntiles / gridDim.x);
+  const int t1 = (int)((long long)(blockIdx.x + 1) * ntiles / gridDim.x);
+  constexpr int G = 16 / R;
+  const int steps = (K + 512 * U - 1) / (512 * U), gs = G * steps;
+  const int nunits = max((t1 - t0 - w + nw - 1) / nw, 0) * gs;  // this wave's tiles: t0 + w, t0 + w + nw, ... < t1
+  typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
+  struct Buf { u32x2v wv[U][R]; float sc[R], cc[R]; };
+  auto issue = [&](int i, Buf& b) {  // rows < 16 * ntiles and columns <= K - 8: inside Qh / scale / cb
+    const int ti = i / gs, rem = i - ti * gs, g = rem / steps, kb = rem - g * steps;
+    const int n0 = (t0 + w + ti * nw) * 16 + g * R;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int col = min((kb * U + u) * 512 + lane * 8, K - 8);
+#pragma unroll
+      for (int r = 0; r < R; r++)
+        b.wv[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x2v*>(Q + (size_t)(n0 + r) * K + col));
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) { b.sc[r] = scale[n0 + r]; b.cc[r] = cb[n0 + r]; }
+  };
+  float4 xv[MM][4];
+  float xc[MM];
+  uint2 gb[4][2];
+  if (threadIdx.x < 256) ln_rows_load<MM>(ln, M, K, xv, xc, gb);
+  // a ring of three buffers: two units (2 x R x U x 512 B per wave, 192 KB per CU at bloom-1b1's width, what the
+  // bf16 head keeps in flight) are on their way while one is computed
+  Buf b0{}, b1{}, b2{};
+  if (nunits > 0) issue(0, b0);
+  if (nunits > 1) issue(1, b1);
+  if (threadIdx.x < 8) xs[(size_t)M * K + threadIdx.x] = (bf16)0.f;  // 16 B of zeros: what a lane past the row's end reads
+  ln_rows_finish<MM>(ln, M, K, xv, xc, gb, xs, scratch);
+  // r_m >= ||x~_m||: fp32 sum of squares (relative error < (K + 2) 2^-24), root, inflated by 2^-10
+  float rm[MM];
+#pragma unroll
+  for (int m = 0; m < MM; m++) {
+    float a = 0.f;
+    for (int k = lane * 8; k < K; k += 512) {
+      float v[8];
+      load8(xs + (size_t)min(m, M - 1) * K + k, v);
+#pragma unroll
+      for (int j = 0; j < 8; j++) a = fmaf(v[j], v[j], a);
+    }
+    rm[m] = sqrtf(wave_sum(a)) * (1.0f + 0x1p-10f);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && m < M) rnorm[m] = rm[m];
+    rm[m] *= 1.0f + 0x1p-20f;
+  }
+  float hi[MM], lo[MM], chk[MM];
+  f2 acc[R][MM];
+#pragma unroll
+  for (int m = 0; m < MM; m++) {
+    hi[m] = -INFINITY; lo[m] = -INFINITY; chk[m] = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r][m] = f2{0.f, 0.f};
+  }
+  auto compute = [&](int i, const Buf& cur) {
+    const int ti = i / gs, rem = i - ti * gs, g = rem / steps, kb = rem - g * steps;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int kk = (kb * U + u) * 512 + lane * 8;
+      f2 xf[MM][4];
+#pragma unroll
+      for (int m = 0; m < MM; m++) {
+        const u32x4v a = *reinterpret_cast<const u32x4v*>(xs + (kk < K ? min(m, M - 1) * K + kk : M * K));
+#pragma unroll
+        for (int j = 0; j < 4; j++) xf[m][j] = f2{__uint_as_float(a[j] << 16), __uint_as_float(a[j] & 0xFFFF0000u)};
+      }
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        // signed bytes -> fp32, exact (sign-extending byte selects of v_cvt_f32_i32: one operation per weight)
+        const int a = (int)cur.wv[u][r].x, b = (int)cur.wv[u][r].y;
+        const f2 wf[4] = {f2{(float)(signed char)a, (float)(signed char)(a >> 8)}, f2{(float)(signed char)(a >> 16), (float)(a >> 24)},
+                          f2{(float)(signed char)b, (float)(signed char)(b >> 8)}, f2{(float)(signed char)(b >> 16), (float)(b >> 24)}};
+#pragma unroll
+        for (int m = 0; m < MM; m++)
+#pragma unroll
+          for (int j = 0; j < 4; j++) acc[r][m] = __builtin_elementwise_fma(xf[m][j], wf[j], acc[r][m]);
+      }
+    }
+    if (kb == steps - 1) {  // the R rows are complete
+#pragma unroll
+      for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int m = 0; m < MM; m++) {
+          const float sh = cur.sc[r] * wave_sum(acc[r][m].x + acc[r][m].y);
+          acc[r][m] = f2{0.f, 0.f};
+          const float e = fmaf(rm[m], cur.cc[r], 0x1p-100f);
+          const float h = sh + e;
+          chk[m] = fmaf(h, 0.f, chk[m]);  // stays 0 while every s^ + E is finite, else NaN (fmaxf would drop a NaN)
+          hi[m] = fmaxf(hi[m], h);
+          lo[m] = fmaxf(lo[m], sh - e);
+        }
+      if (g == G - 1) {
+        const int tile = t0 + w + ti * nw;
+#pragma unroll
+        for (int m = 0; m < MM; m++) {
+          // pushed outwards past the roundings of s^ + E and s^ - E; a non-finite s^ or E: +inf (list every tile)
+          const float h = chk[m] == 0.f ? fmaf(fabsf(hi[m]), 0x1p-22f, hi[m]) : INFINITY;
+          const float l = fmaf(-fabsf(lo[m]), 0x1p-22f, lo[m]);
+          if (lane == 0 && m < M) hilo[(size_t)m * ntiles + tile] = make_float2(h, l);
+          hi[m] = -INFINITY; lo[m] = -INFINITY; chk[m] = 0.f;
+        }
+      }
+    }
+  };
+  for (int i = 0; i < nunits; i += 3) {
+    if (i + 2 < nunits) issue(i + 2, b2);
+    compute(i, b0);
+    if (i + 1 < nunits) {
+      if (i + 3 < nunits) issue(i + 3, b0);
+      compute(i + 1, b1);
+    }
+    if (i + 2 < nunits) {
+      if (i + 4 < nunits) issue(i + 4, b1);
+      compute(i + 2, b2);
+    }
+  }
+}
+
+// (b) Select, one block per row m: L* = max lo, then the tiles with hi >= L*.  A non-finite L*, r_m or hi (or an
+// empty list) lists every tile: garbage input then takes exactly the full head's answer.  Up to 16 tiles per thread
+// (16 384 tiles, V = 262 144) stay in registers: every load is in flight at once and the second pass re-reads
+// nothing (bloom's 15 680 tiles: one memory round trip instead of 32 dependent ones); larger V loops over memory.
+constexpr int kSelPer = 16;
+__global__ __launch_bounds__(1024) void head_select_kernel(const float2* __restrict__ hilo, const float* __restrict__ rnorm,
+                                                           int ntiles, int* __restrict__ list, int* __restrict__ count,
+                                                           float* __restrict__ lstar) {
+  __shared__ float shl[16];
+  __shared__ int shb[16];
+  __shared__ int cnt;
+  const int m = blockIdx.x;
+  const float2* hl = hilo + (size_t)m * ntiles;
+  int* li = list + (size_t)m * ntiles;
+  const bool fits = ntiles <= 1024 * kSelPer;
+  const float r = rnorm[m];
+  float2 v[kSelPer];
+#pragma unroll
+  for (int j = 0; j < kSelPer; j++) v[j] = hl[min((int)threadIdx.x + j * 1024, ntiles - 1)];  // clamped: all in flight
+  float L = -INFINITY;
+  int bad = 0;
+  if (fits) {
+#pragma unroll
+    for (int j = 0; j < kSelPer; j++)
+      if ((int)threadIdx.x + j * 1024 < ntiles) { L = fmaxf(L, v[j].y); bad |= !(fabsf(v[j].x) < INFINITY); }
+  } else {
+    for (int i = threadIdx.x; i < ntiles; i += 1024) {
+      const float2 u = hl[i];
+      L = fmaxf(L, u.y);
+      bad |= !(fabsf(u.x) < INFINITY);
+    }
+  }
+  L = wave_max(L);
+  bad = __any(bad);
+  if ((threadIdx.x & 63) == 0) { shl[threadIdx.x >> 6] = L; shb[threadIdx.x >> 6] = bad; }
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  L = shl[0]; bad = shb[0];
+  for (int j = 1; j < 16; j++) { L = fmaxf(L, shl[j]); bad |= shb[j]; }
+  bool all = bad || !(fabsf(L) < INFINITY) || !(fabsf(r) < INFINITY);
+  if (!all) {  // LDS counter of this block; at most ntiles entries
+    if (fits) {
+#pragma unroll
+      for (int j = 0; j < kSelPer; j++) {
+        const int i = threadIdx.x + j * 1024;
+        if (i < ntiles && v[j].x >= L) li[atomicAdd(&cnt, 1)] = i;
+      }
+    } else {
+      for (int i = threadIdx.x; i < ntiles; i += 1024)
+        if (hl[i].x >= L) li[atomicAdd(&cnt, 1)] = i;
+    }
+    __syncthreads();
+    all = cnt == 0;
+  }
+  if (all)
+    for (int i = threadIdx.x; i < ntiles; i += 1024) li[i] = i;
+  if (threadIdx.x == 0) { count[m] = all ? ntiles : cnt; lstar[m] = L; }
+}
+
+// (c) Re-score: block b takes candidates b, b + grid, ... of every row's list (a bounded loop) and runs the exact
+// head's block body on each with the listed tile in place of blockIdx.x, so keys[m][tile] holds the bit pattern the
+// full head would have written.  (Both rows of an M = 2 step are computed for a tile listed by either; the finalize
+// reads only a row's own list.)
+template <int MM, int U>
+__global__ __launch_bounds__(256) void head_rescore_kernel(const bf16* __restrict__ W, LnArgs ln, int M, int N, int K,
+                                                           Epi ep, const int* __restrict__ list,
+                                                           const int* __restrict__ count, int ntiles) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bool first = true;
+  for (int m = 0; m < M; m++) {
+    const int c = min(max(count[m], 0), ntiles);
+    for (int i = blockIdx.x; i < c; i += gridDim.x) {
+      const int tile = min(max(list[(size_t)m * ntiles + i], 0), ntiles - 1);
+      if (!first) __syncthreads();  // the previous candidate's epilogue still reads the LDS scratch
+      first = false;
+      gemv_rows_block<4, MM, U, X_LN>(W, nullptr, ln, AttnParts{}, M, N, K, ep, tile, smem, nullptr, 0u);
+    }
+  }
+}
+
+// (d) Finalize, one block per row: the max key over the row's listed tiles -> token; advances past_adv like
+// argmax_finalize_kernel (the step's last kernel).
+__global__ __launch_bounds__(1024) void head_screen_finalize_kernel(const unsigned long long* __restrict__ keys, int ntiles,
+                                                                    const int* __restrict__ list,
+                                                                    const int* __restrict__ count, int* tokens,
+                                                                    int* past_adv, int seq) {
+  __shared__ unsigned long long sh[17];
+  const int m = blockIdx.x;
+  const int c = min(max(count[m], 0), ntiles);
+  unsigned long long best = 0;
+  for (int i = threadIdx.x; i < c; i += 1024) {
+    const int tile = min(max(list[(size_t)m * ntiles + i], 0), ntiles - 1);
+    const unsigned long long k = keys[(size_t)m * ntiles + tile];
+    best = k > best ? k : best;
+  }
+  best = block_max_u64(best, sh);
+  if (threadIdx.x == 0) {
+    if (tokens) tokens[m] = (int)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
+    if (past_adv) past_adv[m] += seq;
+  }
+}
+
+bool head_screen_supported(int M, int K) { return M >= 1 && M <= 2 && K % 32 == 0 && K >= 32 && K <= 4096; }
+
+template <int MM>
+static void head_screen_launch(const HeadScreen& hs, const LnArgs& ln, int M, int ntiles, int K, int grid, hipStream_t s) {
+  const size_t shm = 256 + (size_t)M * K * sizeof(bf16) + 16;  // + 16 B of zeros
+  float2* hl = reinterpret_cast<float2*>(hs.hilo);
+  // whole 512-column chunks of a row per unit; R x U <= 12 weight register pairs per buffer (three buffers live),
+  // <= 6 for two rows: every instance stays inside the 128 VGPRs of a 1024-thread block without spilling (ISA metadata)
+  const int cpr = (K + 511) / 512;
+#define HS_GO(UU, RR) gemv_head_screen_kernel<MM, UU, RR><<<grid, 1024, shm, s>>>(hs.Q, hs.scale, hs.cb, ln, M, ntiles, K, hl, hs.rnorm)
+  if (cpr == 1) HS_GO(1, 4);
+  else if (cpr == 2) HS_GO(2, 4);
+  else if (cpr % 5 == 0) HS_GO(5, 2);
+  else if (cpr % 3 == 0) { if constexpr (MM == 1) HS_GO(3, 4); else HS_GO(3, 2); }
+  else HS_GO(4, 2);
+#undef HS_GO
+}
+
+void launch_head_screen(const HeadScreen& hs, const float* x, int row_stride, int row_offset, const void* gamma,
+                        const void* beta, float eps, int M, int V, int K, int cus, hipStream_t s) {
+  const LnArgs ln{x, row_stride, row_offset, (const bf16*)gamma, (const bf16*)beta, eps};
+  const int ntiles = V / 16, grid = std::max(1, std::min(cus, ntiles));
+  if (M == 1) head_screen_launch<1>(hs, ln, M, ntiles, K, grid, s);
+  else head_screen_launch<2>(hs, ln, M, ntiles, K, grid, s);
+}
+
+void launch_head_pick(const HeadScreen& hs, const float* x, int row_stride, int row_offset, const void* gamma,
+                      const void* beta, float eps, const void* W, int M, int V, int K, const Epi& ep, int cus,
+                      int* tokens, int* past_adv, int seq, hipStream_t s) {
+  const LnArgs ln{x, row_stride, row_offset, (const bf16*)gamma, (const bf16*)beta, eps};
+  const int ntiles = V / 16;
+  head_select_kernel<<<M, 1024, 0, s>>>(reinterpret_cast<const float2*>(hs.hilo), hs.rnorm, ntiles, hs.list, hs.count,
+                                        hs.lstar);
+  const size_t shm = 256 + (size_t)M * K * sizeof(bf16);
+  const int grid = 4 * std::max(1, cus);  // four 4-wave blocks per CU: the all-tiles case streams like the full head
+  const bf16* w = (const bf16*)W;
+  // U as the exact head's (gemv_rows_dispatch, EPI_ARGMAX): 4 chunks in flight up to K = 2048, else 2
+  if (K <= 2048) {
+    if (M == 1) head_rescore_kernel<1, 4><<<grid, 256, shm, s>>>(w, ln, M, V, K, ep, hs.list, hs.count, ntiles);
+    else head_rescore_kernel<2, 4><<<grid, 256, shm, s>>>(w, ln, M, V, K, ep, hs.list, hs.count, ntiles);
+  } else {
+    if (M == 1) head_rescore_kernel<1, 2><<<grid, 256, shm, s>>>(w, ln, M, V, K, ep, hs.list, hs.count, ntiles);
+    else head_rescore_kernel<2, 2><<<grid, 256, shm, s>>>(w, ln, M, V, K, ep, hs.list, hs.count, ntiles);
+  }
+  head_screen_finalize_kernel<<<M, 1024, 0, s>>>(ep.keys, ntiles, hs.list, hs.count, tokens, past_adv, seq);
 }

@@ -92,6 +92,12 @@ struct ProfClass {
 constexpr size_t kSkCap = (size_t)1024 * 128 * 128;
 constexpr int kSkTickets = 4096;
 
+// BS_HEAD_SCREEN=0 (read once): stages start with the greedy head screening off (A/B runs).
+static int head_screen_default() {
+  static const int v = [] { const char* e = getenv("BS_HEAD_SCREEN"); return (e && e[0] == '0') ? 0 : 1; }();
+  return v;
+}
+
 static int graphs_default() {
   const char* e = getenv("BS_GRAPHS");
   return (e && e[0] == '0') ? 0 : 1;
@@ -160,6 +166,14 @@ struct bs_stage {
   // set (rocprofv3 --pmc runs: rocprofiler-sdk's counter-collection dispatch interception faulted on graph-launched
   // kernels)
   int graphs_on = graphs_default();
+  // greedy lm_head screening (kernels.hip "Greedy lm_head screening"): the int8 shadow copy of the tied embedding,
+  // its bound constants and the per-step buffers, one allocation made at init (null: none, screening stays off)
+  char* hs_base = nullptr;
+  size_t hs_bytes = 0;
+  HeadScreen hs{};
+  int hs_on = 0;         // bs_set_head_screen; starts on where the shadow copy exists (and BS_HEAD_SCREEN is not 0)
+  int hs_last_rows = 0;  // rows of the last forward if its tail ran screened, else 0 (bs_read_head_screen)
+  int cus = 0;           // CUs of the device (grids of the screened tail)
 };
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -277,6 +291,7 @@ static void free_stage(bs_stage* s) {
   if (s->logit_buf) hipFree(s->logit_buf);
   if (s->sample_logits) hipFree(s->sample_logits);
   if (s->wtmp) hipFree(s->wtmp);
+  if (s->hs_base) hipFree(s->hs_base);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
@@ -592,6 +607,32 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
     hipFree(bounce);
   }
 
+  // ---- greedy lm_head screening: int8 shadow copy of the resident bf16 embedding (the BS_FLAG_INT8_WEIGHTS rule),
+  // one bound constant per row, and the per-step buffers for up to 2 rows.  A failed allocation leaves it off.
+  if (s->bf16 && desc->is_last && !s->n_labels && s->wemb && head_screen_supported(1, (int)h) &&
+      hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, desc->device) == hipSuccess && s->cus > 0) {
+    const size_t nt = V / 16, mb = std::min<size_t>(desc->max_batch, 2);
+    const size_t sizes[8] = {V * h, V * 4, V * 4, mb * nt * 8, mb * 4, mb * 4, mb * nt * 4, mb * 4};
+    size_t ho[8], hoff = 0;
+    for (int i = 0; i < 8; i++) { ho[i] = hoff; hoff = align_up(hoff + sizes[i], 256); }
+    if (hipMalloc(&s->hs_base, hoff) == hipSuccess) {
+      s->hs_bytes = hoff;
+      int8_t* Qh = (int8_t*)(s->hs_base + ho[0]);
+      float* sch = (float*)(s->hs_base + ho[1]);
+      float* cbh = (float*)(s->hs_base + ho[2]);
+      s->hs = HeadScreen{Qh, sch, cbh, (float*)(s->hs_base + ho[3]), (float*)(s->hs_base + ho[4]),
+                         (float*)(s->hs_base + ho[5]), (int*)(s->hs_base + ho[6]), (int*)(s->hs_base + ho[7])};
+      if (hipMemsetAsync(s->hs_base + ho[3], 0, hoff - ho[3], s->own) != hipSuccess)
+        return cleanup(fail(BS_ERR_DEVICE, "head screen memset"));
+      launch_quantize_rows(s->wemb, Qh, sch, (int)V, (int)h, s->own);
+      launch_head_bound(s->wemb, Qh, sch, cbh, (int)V, (int)h, s->own);
+      s->hs_on = head_screen_default();
+    } else {
+      (void)hipGetLastError();  // not an init failure
+      s->hs_base = nullptr;
+    }
+  }
+
   // ---- KV cache
   s->kv_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx * s->hd * s->esz;
   s->kv_layer_stride = 2 * s->kv_half;
@@ -663,7 +704,7 @@ extern "C" int bs_stage_info(const bs_stage* s, bs_stage_desc* d, uint64_t* wb, 
   if (d) *d = s->d;
   if (wb) *wb = s->wbytes;
   if (kvb) *kvb = s->kvbytes;
-  if (wsb) *wsb = s->wsbytes;
+  if (wsb) *wsb = s->wsbytes + s->hs_bytes;  // the head-screening shadow copy counts as workspace, not weights
   return BS_OK;
 }
 
@@ -1045,6 +1086,12 @@ static void wlinear_ln(bs_stage* s, hipStream_t st, const float* x, const void* 
   wlinear(s, st, s->xn, w, t, M, N, K, ep, out_bytes);
 }
 
+// Does a forward of B rows take the screened greedy tail (else the full head)?
+static bool head_screened(const bs_stage* s, int B, bool want_logits) {
+  return s->hs_on && s->hs_base && s->d.is_last && !s->n_labels && s->top_k <= 1 && !want_logits &&
+         head_screen_supported(B, s->d.hidden);
+}
+
 // Device staging for logits requested with host I/O: one buffer per stage, grown on demand (a
 // stream-ordered hipMallocAsync/hipFreeAsync pair per call handed blocks across the streams of
 // two stages and returned zeros on ROCm 7.2; this is also cheaper).
@@ -1184,14 +1231,27 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
       e.logits = dev_logits;
     }
     if (sample && !e.logits) e.logits = s->sample_logits;
-    linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, s->wemb, B, V, h, with_splitk(s, e), 0);
     int* tok_out = host_io ? s->tok : (int*)out;
-    // the pick is the step's last kernel: it advances the device copy of every row's past_len by S
-    if (sample)
-      launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
-                         past_dev, S, tok_out, st, s->past_dev);
-    else
-      launch_argmax_finalize(s->keys, B, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S);
+    const bool screened = head_screened(s, B, want_logits);
+    if (screened) {
+      // greedy, no logits, <= 2 rows: int8 screening pass, then the exact head on the few tiles that can win
+      {  // class 1 counts the bytes the screen really streams: int8 rows, scales, bound constants, rows in, hi/lo out
+        ProfScope p(s, st, 1, (double)V * h + 8.0 * V + (double)B * h * 4 + (double)B * (V / 16) * 8);
+        launch_head_screen(s->hs, cur, S, S - 1, s->lnf_g, s->lnf_b, d.ln_eps, B, V, h, s->cus, st);
+      }
+      // select + re-score + finalize stay outside class 1 (the candidate count is known on the device only);
+      // the finalize is the step's last kernel and advances past_dev by S
+      launch_head_pick(s->hs, cur, S, S - 1, s->lnf_g, s->lnf_b, d.ln_eps, s->wemb, B, V, h, e, s->cus, tok_out,
+                       s->past_dev, S, st);
+    } else {
+      linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, s->wemb, B, V, h, with_splitk(s, e), 0);
+      // the pick is the step's last kernel: it advances the device copy of every row's past_len by S
+      if (sample)
+        launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
+                           past_dev, S, tok_out, st, s->past_dev);
+      else
+        launch_argmax_finalize(s->keys, B, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S);
+    }
     if (host_io) {
       HIP_TRY(hipMemcpyAsync(out, s->tok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
       if (dev_logits) HIP_TRY(hipMemcpyAsync(logits, dev_logits, (size_t)B * V * 4, hipMemcpyDeviceToHost, st));
@@ -1263,6 +1323,32 @@ extern "C" int bs_set_graphs(bs_stage* s, int32_t on) {
   for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
   s->graphs.clear();
   s->graphs_on = on ? 1 : 0;
+  return BS_OK;
+}
+
+extern "C" int bs_set_head_screen(bs_stage* s, int32_t on) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (on && !s->hs_base) return fail(BS_ERR_STATE, "stage holds no head shadow copy (bf16 last stage with the whole lm_head)");
+  HIP_TRY(hipSetDevice(s->d.device));
+  // captured decode graphs hold the old tail
+  HIP_TRY(hipDeviceSynchronize());
+  for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
+  s->graphs.clear();
+  s->hs_on = on ? 1 : 0;
+  return BS_OK;
+}
+
+extern "C" int bs_read_head_screen(bs_stage* s, int32_t row, float* hilo, float* lstar, int32_t* list, int32_t* count) {
+  if (!s || !count) return fail(BS_ERR_INVALID, "stage/count is NULL");
+  if (s->hs_last_rows <= 0) { *count = -1; return BS_OK; }  // the last forward took the full head
+  if (row < 0 || row >= s->hs_last_rows) return fail(BS_ERR_INVALID, "row outside the last forward");
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t nt = (size_t)s->d.vocab / 16;
+  if (hilo) HIP_TRY(hipMemcpy(hilo, s->hs.hilo + (size_t)row * nt * 2, nt * 8, hipMemcpyDeviceToHost));
+  if (lstar) HIP_TRY(hipMemcpy(lstar, s->hs.lstar + row, 4, hipMemcpyDeviceToHost));
+  if (list) HIP_TRY(hipMemcpy(list, s->hs.list + (size_t)row * nt, nt * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(count, s->hs.count + row, 4, hipMemcpyDeviceToHost));
   return BS_OK;
 }
 
@@ -1345,6 +1431,7 @@ extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void
   BS_TRACE("hipGetLastError");
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
+  s->hs_last_rows = head_screened(s, B, want_logits) ? B : 0;
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)
     s->past_next.assign(pasts.begin(), pasts.end());
     for (int& p : s->past_next) p += S;

@@ -85,7 +85,7 @@ EXPORTS = [
     "bs_codec_serialize", "bs_codec_deserialize", "bs_dtype_size", "bs_serialize_int", "bs_deserialize_int",
     "bs_prompt_ids", "bs_read_weights", "bs_head_norm", "bs_head_slice", "bs_stream_delay", "bs_set_sampling",
     "bs_build_id", "bs_hbm_probe", "bs_mfma_probe", "bs_init_stage_file", "bs_weights_file_probe",
-    "bs_set_graphs", "bs_binary_classify",
+    "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
 ]
 
 _LIB = None
@@ -139,6 +139,8 @@ def lib():
         L.bs_head_slice.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         L.bs_set_sampling.argtypes = [vp, i32, ctypes.c_float, ctypes.c_uint64]
         L.bs_set_graphs.argtypes = [vp, i32]
+        L.bs_set_head_screen.argtypes = [vp, i32]
+        L.bs_read_head_screen.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(i32)]
         L.bs_hbm_probe.argtypes = [i32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         L.bs_mfma_probe.argtypes = [i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         _LIB = L
@@ -269,6 +271,27 @@ class Stage:
     def set_graphs(self, on=True):
         """bs_set_graphs: replay captured decode graphs (default) or launch every step eagerly."""
         _check(lib().bs_set_graphs(self._h, 1 if on else 0))
+
+    def set_head_screen(self, on=True):
+        """bs_set_head_screen: greedy steps of <= 2 rows screen the lm_head on its int8 shadow copy and re-score
+        the few candidate tiles exactly (default where the copy exists), or always run the full head."""
+        _check(lib().bs_set_head_screen(self._h, 1 if on else 0))
+
+    def read_head_screen(self, row=0):
+        """bs_read_head_screen for row `row` of the last forward: None when its tail took the full head, else
+        {"hi", "lo": fp32 [vocab/16] bounds of each 16-row tile's largest logit, "lstar": the largest lo,
+        "tiles": the candidate tiles, sorted}."""
+        nt = self.vocab // 16
+        hilo = np.empty((nt, 2), np.float32)
+        lstar = np.empty(1, np.float32)
+        tiles = np.empty(nt, np.int32)
+        n = ctypes.c_int32()
+        _check(lib().bs_read_head_screen(self._h, row, hilo.ctypes.data, lstar.ctypes.data, tiles.ctypes.data,
+                                         ctypes.byref(n)))
+        if n.value < 0:
+            return None
+        return {"hi": hilo[:, 0].copy(), "lo": hilo[:, 1].copy(), "lstar": float(lstar[0]),
+                "tiles": np.sort(tiles[:n.value])}
 
     # ---- vocabulary-parallel head (device pointers, stream ordered)
     def head_norm(self, hidden, batch, seq, xn, stream=None):

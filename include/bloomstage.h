@@ -194,6 +194,23 @@ int bs_set_sampling(bs_stage *stage, int32_t top_k, float temperature, uint64_t 
  * when the environment holds BS_GRAPHS=0 at bs_init_stage (rocprofv3 --pmc runs). */
 int bs_set_graphs(bs_stage *stage, int32_t on);
 
+/* ---- Greedy head screening ----
+ * A bf16 last stage of a generation model keeps, besides the bf16 tied lm_head, an int8 shadow copy of it (the
+ * BS_FLAG_INT8_WEIGHTS rule) with one rigorous error-bound constant per vocabulary row, built once at init and
+ * counted under workspace_bytes of bs_stage_info.  A greedy forward (top_k <= 1) of at most 2 rows that requests no
+ * logits streams the int8 copy, marks the 16-row tiles that cannot hold the largest logit, and runs the exact bf16
+ * head on the remaining tiles only: the token ids are bit-identical to the full head's (first index on ties); logits,
+ * sampling and every other shape take the full head.  on = 0 always takes the full head (for A/B runs and debugging);
+ * on = 1 needs the shadow copy (BS_ERR_STATE otherwise: fp32 or classifier stages, hidden > 4096, or an allocation
+ * that failed at init).  Synchronizes and drops captured graphs.  A stage starts with screening on where the shadow
+ * copy exists, unless the environment holds BS_HEAD_SCREEN=0 (read once per process). */
+int bs_set_head_screen(bs_stage *stage, int32_t on);
+/* Read-out of the stage's last forward, for verification: *count = -1 when its tail took the full head; otherwise,
+ * for row `row` of that forward, hilo[vocab/16][2] = per 16-row tile (upper bound of the tile's largest logit, lower
+ * bound of it), *lstar = the largest lower bound, list[0..*count) = the candidate tiles (unordered; list needs room
+ * for vocab/16 entries).  hilo, lstar and list may be NULL.  Synchronizes the device. */
+int bs_read_head_screen(bs_stage *stage, int32_t row, float *hilo, float *lstar, int32_t *list, int32_t *count);
+
 /* Forget the cached positions of one KV row (slot), or of all rows when slot < 0. */
 int bs_reset_kv(bs_stage *stage, int32_t slot);
 /* Read back KV row `slot` of the stage's local layer `layer`, positions [pos0, pos0 + npos), as fp32
