@@ -44,8 +44,14 @@ def get(name: str) -> BloomDims:
     return replace(m, name=m.name + "-int8", int8_weights=True) if int8 else m
 
 
+def kv_bytes_per_element(m: BloomDims, kv_int8: bool = False) -> float:
+    """HBM bytes per cached K/V element: 2 (bf16), or 1 + 4 / head_dim for the int8 cache (one int8 code per element
+    and one fp32 scale per (position, head) vector, BS_FLAG_INT8_KV).  Feeds decode_step_bytes' kv_bytes."""
+    return 1.0 + 4.0 / m.head_dim if kv_int8 else 2.0
+
+
 def decode_step_bytes(m: BloomDims, layers: int, batch: int, ctx: int, first: bool, last: bool,
-                      w_bytes: int = 2, kv_bytes: int = 2, act_bytes: int = 4) -> float:
+                      w_bytes: int = 2, kv_bytes: float = 2, act_bytes: int = 4) -> float:
     """Algorithmic HBM bytes of one decode step of a stage (BASELINE.md / SURVEY §8d):
     sum_layers[(12h^2+13h)w + 2*B*ctx*h*k (KV read) + 2*B*h*k (KV write)]
     + [first](B*h*w + 4h*w... emb row gather + emb LN) + [last](V*h*w + 2h*w) + 2*B*h*act."""

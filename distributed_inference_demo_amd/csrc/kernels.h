@@ -108,6 +108,26 @@ size_t attention_workspace_floats(int B, int n_head, int head_dim, int max_ctx, 
 // Context splits per (row, head) of a decode attention launch (1 = the block writes ctx itself).
 int attention_decode_splits(int B, int n_head, int max_chunks);
 
+// ---- Int8 KV cache (bf16 stages with BS_FLAG_INT8_KV; kv_int8.hip) ----
+// The fp32 scales beside the int8 codes of one layer ([max_batch][heads][max_ctx], K and V), and the bf16 staging
+// buffers the QKV epilogue writes a call's new K / V rows to ([B][heads][lmax][hd], slot 0).
+struct KvQ8 {
+  float* k_scale;
+  float* v_scale;
+  __bf16* k_stage;
+  __bf16* v_stage;
+};
+// S == 1: decode attention over the int8 cache (a.k_cache / a.v_cache = the layer's codes); the new token comes from
+// staging [B][heads][1][hd] and is quantised into the cache at past_b by one block per (row, head).  Grids, partials
+// and finishes are launch_attention's.
+void launch_attention_q8(const AttnArgs& a, const KvQ8& kq, hipStream_t s);
+// S > 1: cache positions [0, past_b) of rows slot.. -> staging (bf16((float)q * scale)); past_max = max_b past_b.
+void launch_kv_dequant(const void* k_codes, const void* v_codes, const KvQ8& kq, const int* past_dev, int B, int slot,
+                       int n_head, int head_dim, int max_ctx, int lmax, int past_max, hipStream_t s);
+// S > 1: staging positions past_b .. past_b + S - 1 -> codes and scales at the same cache positions.
+void launch_kv_quant(void* k_codes, void* v_codes, const KvQ8& kq, const int* past_dev, int B, int S, int slot,
+                     int n_head, int head_dim, int max_ctx, int lmax, hipStream_t s);
+
 // Split-attention partials as the consumer reads them (attn_merge.h).
 struct AttnParts {
   const float* acc;  // AttnArgs::part_acc

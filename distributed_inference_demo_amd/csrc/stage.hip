@@ -107,6 +107,7 @@ struct bs_stage {
   bs_stage_desc d;
   int bf16 = 1;
   int q8 = 0;              // BS_FLAG_INT8_WEIGHTS: block matrices int8 + row scales
+  int kv8 = 0;             // BS_FLAG_INT8_KV: int8 KV codes + fp32 scales, bf16 staging (kv_int8.hip)
   size_t esz = 2;
   void* wtmp = nullptr;    // int8 stages: bf16 [4h][h] staging (init) and dequantized operand (prefill)
   int hd = 0, L = 0;
@@ -125,6 +126,13 @@ struct bs_stage {
   int n_labels = 0;
   std::vector<Layer> layers;
   char* kv = nullptr;  // [L][2][max_batch][heads][max_ctx][hd]
+  // BS_FLAG_INT8_KV: kv holds the int8 codes in that layout (kv_half / kv_layer_stride in bytes of codes), then the
+  // fp32 scales [L][2][max_batch][heads][max_ctx] at kv_scales; kv_stage: two bf16 staging buffers (K, V) of
+  // kv_stage_cap positions x hidden each, shared by the layers
+  float* kv_scales = nullptr;
+  size_t kv_sc_half = 0;       // scales of K (or V) of one layer
+  char* kv_stage = nullptr;
+  size_t kv_stage_cap = 0;
   size_t kvbytes = 0;
   size_t kv_layer_stride = 0;  // bytes per (layer) = 2 * half
   size_t kv_half = 0;          // bytes for K (or V) of one layer
@@ -231,7 +239,12 @@ static int validate(const bs_stage_desc* d, bool from_file = false) {
     return fail(BS_ERR_INVALID, "head vocab slice must be a 16-aligned sub-range of [0, vocab)");
   if (!from_file && d->weight_source != BS_WEIGHTS_SYNTHETIC && d->weight_source != BS_WEIGHTS_HOST)
     return fail(BS_ERR_INVALID, "unknown weight_source");
-  if (d->flags & ~(BS_FLAG_INT8_WEIGHTS | BS_FLAG_CLASSIFIER)) return fail(BS_ERR_INVALID, "unknown desc flags");
+  if (d->flags & ~(BS_FLAG_INT8_WEIGHTS | BS_FLAG_CLASSIFIER | BS_FLAG_INT8_KV))
+    return fail(BS_ERR_INVALID, "unknown desc flags");
+  if ((d->flags & BS_FLAG_INT8_KV) && d->dtype != BS_DT_BFLOAT16)
+    return fail(BS_ERR_INVALID, "BS_FLAG_INT8_KV needs dtype BFLOAT16");
+  if ((d->flags & BS_FLAG_INT8_KV) && hd % 16)
+    return fail(BS_ERR_UNSUPPORTED, "BS_FLAG_INT8_KV needs head_dim to be a multiple of 16");
   if (d->flags & BS_FLAG_CLASSIFIER) {
     if (!d->is_last) return fail(BS_ERR_INVALID, "BS_FLAG_CLASSIFIER needs the last stage");
     if (d->n_labels < 1 || d->n_labels > 64) return fail(BS_ERR_INVALID, "n_labels must be in [1, 64]");
@@ -287,6 +300,7 @@ static void free_stage(bs_stage* s) {
   for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
   if (s->wbase) hipFree(s->wbase);
   if (s->kv) hipFree(s->kv);
+  if (s->kv_stage) hipFree(s->kv_stage);
   if (s->ws) hipFree(s->ws);
   if (s->logit_buf) hipFree(s->logit_buf);
   if (s->sample_logits) hipFree(s->sample_logits);
@@ -419,6 +433,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   if (s->d.max_tokens <= 0) s->d.max_tokens = s->d.max_batch * 128;
   s->bf16 = desc->dtype == BS_DT_BFLOAT16;
   s->q8 = (desc->flags & BS_FLAG_INT8_WEIGHTS) != 0;
+  s->kv8 = (desc->flags & BS_FLAG_INT8_KV) != 0;
   s->esz = s->bf16 ? 2 : 4;
   s->n_labels = (desc->flags & BS_FLAG_CLASSIFIER) ? desc->n_labels : 0;
   s->hd = desc->hidden / desc->n_head;
@@ -634,13 +649,25 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   }
 
   // ---- KV cache
-  s->kv_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx * s->hd * s->esz;
+  s->kv_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx * s->hd * (s->kv8 ? 1 : s->esz);
   s->kv_layer_stride = 2 * s->kv_half;
   s->kvbytes = s->kv_layer_stride * (s->L > 0 ? s->L : 0);
+  if (s->kv8) {  // the scales follow the codes (16-B aligned: head_dim % 16 == 0)
+    s->kv_sc_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx;
+    s->kvbytes += 2 * s->kv_sc_half * 4 * (s->L > 0 ? s->L : 0);
+  }
   if (s->kvbytes) {
     if (hipMalloc(&s->kv, s->kvbytes) != hipSuccess)
       return cleanup(fail(BS_ERR_OOM, "KV cache allocation failed (" + std::to_string(s->kvbytes) + " B)"));
     if (hipMemsetAsync(s->kv, 0, s->kvbytes, s->own) != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, "kv memset"));
+    if (s->kv8) s->kv_scales = (float*)(s->kv + s->kv_layer_stride * s->L);
+  }
+  if (s->kv8 && s->L > 0) {  // bf16 staging of a call's new K / V rows (and, for S > 1, the dequantised past)
+    s->kv_stage_cap = std::max<size_t>(T, desc->max_ctx);
+    const size_t sb = 2 * s->kv_stage_cap * h * 2;
+    if (hipMalloc(&s->kv_stage, sb) != hipSuccess)
+      return cleanup(fail(BS_ERR_OOM, "KV staging allocation failed (" + std::to_string(sb) + " B)"));
+    if (hipMemsetAsync(s->kv_stage, 0, sb, s->own) != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, "kv staging memset"));
   }
 
   // ---- workspace
@@ -704,7 +731,8 @@ extern "C" int bs_stage_info(const bs_stage* s, bs_stage_desc* d, uint64_t* wb, 
   if (d) *d = s->d;
   if (wb) *wb = s->wbytes;
   if (kvb) *kvb = s->kvbytes;
-  if (wsb) *wsb = s->wsbytes + s->hs_bytes;  // the head-screening shadow copy counts as workspace, not weights
+  // the head-screening shadow copy and the int8 KV staging count as workspace
+  if (wsb) *wsb = s->wsbytes + s->hs_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
   return BS_OK;
 }
 
@@ -758,10 +786,22 @@ extern "C" int bs_read_kv(const bs_stage* s, int32_t layer, int32_t slot, int32_
   HIP_TRY(hipStreamSynchronize(s->own));
   const int nh = s->d.n_head, hd = s->hd;
   const size_t run = (size_t)npos * hd;  // contiguous elements of one (K|V, head)
-  std::vector<uint16_t> tmp(s->bf16 ? run : 0);
+  std::vector<uint16_t> tmp(s->bf16 && !s->kv8 ? run : 0);
+  std::vector<int8_t> qtmp(s->kv8 ? run : 0);
+  std::vector<float> stmp(s->kv8 ? npos : 0);
   for (int w = 0; w < 2; w++)
     for (int hh = 0; hh < nh; hh++) {
       const size_t e0 = (((size_t)slot * nh + hh) * s->d.max_ctx + pos0) * hd;
+      if (s->kv8) {  // dequantised values: (float)q * scale
+        float* dq = out + ((size_t)w * nh + hh) * run;
+        if (!run) continue;
+        HIP_TRY(hipMemcpy(qtmp.data(), s->kv + layer * s->kv_layer_stride + w * s->kv_half + e0, run,
+                          hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(stmp.data(), s->kv_scales + ((size_t)layer * 2 + w) * s->kv_sc_half + e0 / hd,
+                          (size_t)npos * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < run; i++) dq[i] = (float)qtmp[i] * stmp[i / hd];
+        continue;
+      }
       const char* src = s->kv + layer * s->kv_layer_stride + w * s->kv_half + e0 * s->esz;
       float* dst = out + ((size_t)w * nh + hh) * run;
       if (s->bf16) {
@@ -783,12 +823,17 @@ extern "C" int bs_reset_kv(bs_stage* s, int32_t slot) {
   HIP_TRY(hipSetDevice(s->d.device));
   // Cached positions are addressed by past_len, so forgetting is bookkeeping only; zero the
   // rows anyway so stale data can never be read by a caller that reuses past_len wrongly.
-  const size_t row = (size_t)s->d.n_head * s->d.max_ctx * s->hd * s->esz;
+  const size_t row = (size_t)s->d.n_head * s->d.max_ctx * s->hd * (s->kv8 ? 1 : s->esz);
+  const size_t srow = (size_t)s->d.n_head * s->d.max_ctx;  // int8 KV: scales of one row
   for (int l = 0; l < s->L; l++)
     for (int w = 0; w < 2; w++) {
       char* base = s->kv + l * s->kv_layer_stride + w * s->kv_half;
       if (slot < 0) HIP_TRY(hipMemsetAsync(base, 0, s->kv_half, s->own));
       else HIP_TRY(hipMemsetAsync(base + (size_t)slot * row, 0, row, s->own));
+      if (!s->kv8) continue;
+      float* sc = s->kv_scales + ((size_t)l * 2 + w) * s->kv_sc_half;
+      if (slot < 0) HIP_TRY(hipMemsetAsync(sc, 0, s->kv_sc_half * 4, s->own));
+      else HIP_TRY(hipMemsetAsync(sc + (size_t)slot * srow, 0, srow * 4, s->own));
     }
   HIP_TRY(hipStreamSynchronize(s->own));
   return BS_OK;
@@ -1151,6 +1196,18 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     e.kind = EPI_QKV; e.bias = w.t[T_QKV_B]; e.q_out = s->q; e.k_cache = kbase; e.v_cache = kbase + s->kv_half;
     e.hidden = h; e.head_dim = hd; e.max_ctx = d.max_ctx; e.n_head = nh; e.seq = S; e.slot = slot; e.past = past;
     e.past_dev = past_dev; e.ldo = 3 * h;
+    // int8 KV: the epilogue writes the call's bf16 K / V rows to staging [B][head][lmax][hd]; S == 1 keeps one
+    // position per (row, head) at static arguments (graph-capturable), S > 1 lays each row out as the prefill
+    // attention reads it: its dequantised past, then the new positions at past_b ..
+    KvQ8 kq{};
+    const int past_max = *std::max_element(pasts.begin(), pasts.end());
+    const int lmax = S == 1 ? 1 : past_max + S;
+    if (s->kv8) {
+      kq.k_scale = s->kv_scales + (size_t)l * 2 * s->kv_sc_half; kq.v_scale = kq.k_scale + s->kv_sc_half;
+      kq.k_stage = (bf16*)s->kv_stage; kq.v_stage = kq.k_stage + s->kv_stage_cap * h;
+      e.k_cache = kq.k_stage; e.v_cache = kq.v_stage; e.slot = 0; e.max_ctx = lmax;
+      if (S == 1) { e.past_dev = nullptr; e.past = 0; }
+    }
     bool done = false;
     if (l == 0 && emb_fused) {
       ProfScope p(s, st, 1, gemv_bytes(s, M, 3 * h, h, 4) + (double)M * h * (s->esz + 4));
@@ -1177,9 +1234,19 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     // a = x + dense(ctx)
     Epi e2{};
     e2.kind = EPI_RESID; e2.bias = w.t[T_DENSE_B]; e2.out_f32 = s->attn; e2.resid = cur; e2.ldo = h;
-    {
+    if (!s->kv8) {
       ProfScope p(s, st, 3, ctx_sum * nh * hd * 2 * s->esz);
       launch_attention(s->bf16, a, st);
+    } else if (S == 1) {
+      ProfScope p(s, st, 3, ctx_sum * nh * 2 * (hd + 4));
+      launch_attention_q8(a, kq, st);
+    } else {
+      ProfScope p(s, st, 3, ctx_sum * nh * 2 * (hd + 4));
+      launch_kv_dequant(kbase, kbase + s->kv_half, kq, past_dev, B, slot, nh, hd, d.max_ctx, lmax, past_max, st);
+      AttnArgs as = a;
+      as.k_cache = kq.k_stage; as.v_cache = kq.v_stage; as.slot = 0; as.max_ctx = lmax;
+      launch_attention(1, as, st);
+      launch_kv_quant(kbase, kbase + s->kv_half, kq, past_dev, B, S, slot, nh, hd, d.max_ctx, lmax, st);
     }
     if (a.defer_merge) {
       const AttnParts parts{s->part_acc, s->part_ml, nsplit, nh, hd, s->max_chunks, slot};
@@ -1365,6 +1432,13 @@ extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void
     if (pasts[b] < 0 || pasts[b] + S > d.max_ctx) return fail(BS_ERR_INVALID, "past_len + seq exceeds max_ctx");
   }
   if (M > d.max_tokens) return fail(BS_ERR_INVALID, "batch*seq exceeds max_tokens");
+  if (s->kv8 && S > 1 && s->L > 0) {  // every row's past and new positions side by side in the bf16 staging
+    const size_t need = (size_t)B * (*std::max_element(pasts.begin(), pasts.end()) + S);
+    if (need > s->kv_stage_cap)
+      return fail(BS_ERR_UNSUPPORTED, "int8 KV: batch * (longest past_len + seq) = " + std::to_string(need) +
+                                          " positions exceed the staging capacity of " +
+                                          std::to_string(s->kv_stage_cap) + " (max(max_tokens, max_ctx))");
+  }
   if (!in || !out) return fail(BS_ERR_INVALID, "in/out is NULL");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   if (want_logits && (!d.is_last || !logits)) return fail(BS_ERR_INVALID, "logits requested on a non-last stage or NULL");

@@ -434,11 +434,11 @@ def connect_p2p(rank, world, head_split, groups, device):
 
 
 def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb_rows=1, n_mb=None, max_ctx=1024,
-               max_seq=512, seed=0, head_split=None, executor_factory=None, n_labels=0):
+               max_seq=512, seed=0, head_split=None, executor_factory=None, n_labels=0, kv_int8=False):
     """Create this rank's stage (server.py:893-905 layer range, plus a vocabulary slice of the
     tied lm_head when head_split) and its Pipeline.  n_labels > 0: the last stage is a sequence-classification
-    tail (BS_FLAG_CLASSIFIER; `classify` runs the task) and there is no head ring.  Collective: every rank must
-    call it."""
+    tail (BS_FLAG_CLASSIFIER; `classify` runs the task) and there is no head ring.  kv_int8: every stage keeps an
+    int8 KV cache (BS_FLAG_INT8_KV; bf16 stages of the HIP library only).  Collective: every rank must call it."""
     if n_labels and head_split:
         raise ValueError("a classifier tail holds its own score head: no vocabulary-parallel head ring")
     head_split = (world > 1 and not n_labels) if head_split is None else (head_split and world > 1)
@@ -450,7 +450,13 @@ def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb
                          "leave a slice without a 16-column tile")
     if model.int8_weights and dtype != "bf16":
         raise ValueError(f"{model.name}: weight-only int8 stages need dtype bf16 (got {dtype})")
+    if kv_int8 and dtype != "bf16":
+        raise ValueError(f"an int8 KV cache needs dtype bf16 (got {dtype})")
+    if kv_int8 and executor_factory is not None:
+        raise ValueError("an int8 KV cache is the HIP stage's: not available with an executor_factory")
     lb, le = stage_ranges(world, model.n_layer)[rank]
+    if kv_int8 and le <= lb:  # defensive: stage_ranges gives every rank a layer (checked above)
+        raise ValueError("an int8 KV cache on a stage that holds only a vocabulary slice (no layers, no cache)")
     is_first, is_last = rank == 0, rank == world - 1
     hslice = vocab_slices(model.vocab, world)[rank] if head_split else None
     if executor_factory is None:
@@ -459,7 +465,7 @@ def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb
                    device=device.index if device.type == "cuda" else 0, max_batch=mb_rows * n_mb,
                    max_ctx=max_ctx, max_tokens=mb_rows * max_seq, seed=seed, is_first=is_first,
                    is_last=is_last and not head_split, head_slice=hslice, int8_weights=model.int8_weights,
-                   n_labels=n_labels if is_last else 0)
+                   n_labels=n_labels if is_last else 0, kv_int8=kv_int8)
         ex = StageExecutor(st)
     else:
         kw = {"n_labels": n_labels} if (n_labels and is_last) else {}

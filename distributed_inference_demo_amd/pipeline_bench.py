@@ -80,7 +80,7 @@ def _progress(msg):
 
 
 def run_pipeline(model, rank, world, dev, *, mb_rows, n_mb, head_split, prompts, steps, warmup, dtype="bf16",
-                 seed=0, prof_rounds=0, executor_factory=None, replica=False, last_tokens=None):
+                 seed=0, prof_rounds=0, executor_factory=None, replica=False, last_tokens=None, kv_int8=False):
     """Build this rank's stage + Pipeline once, then for each prompt length P in `prompts`: a timed P-token
     prefill round (every micro-batch streams through the stages; per-stage forward times), `warmup` and
     `steps` timed decode rounds (barrier + sync on both sides, max over ranks).  After the first point,
@@ -90,14 +90,16 @@ def run_pipeline(model, rank, world, dev, *, mb_rows, n_mb, head_split, prompts,
     communication on the data path) and runs n_mb x mb_rows rows of its own; the timing brackets (barrier +
     sync, max over ranks) are the same, and the record's value counts the rows of all ranks.
     last_tokens (a list): rank 0 appends, per prompt length, the tokens the last timed round returned to it
-    (int32 [n_mb * mb_rows] on the host) -- bench.py's --dump-outputs."""
+    (int32 [n_mb * mb_rows] on the host) -- bench.py's --dump-outputs.
+    kv_int8: the stages keep an int8 KV cache (BS_FLAG_INT8_KV); the byte model counts its codes and scales."""
     W, K = warmup, steps
     pmax = max(prompts)
     b_rank, b_world = (0, 1) if replica else (rank, world)
     _progress(f"{model.name}: build (mb_rows {mb_rows}, n_mb {n_mb}, prompts {list(prompts)})")
     pipe, (lb, le) = build_rank(model, b_rank, b_world, dev, dtype=dtype, mb_rows=mb_rows, n_mb=n_mb,
                                 max_ctx=pmax + W + K + prof_rounds + 2, max_seq=pmax, seed=seed,
-                                head_split=head_split and not replica, executor_factory=executor_factory)
+                                head_split=head_split and not replica, executor_factory=executor_factory,
+                                kv_int8=kv_int8)
     cuda = dev.type == "cuda"
     prev = torch.cuda.current_stream() if cuda else None
     if cuda:
@@ -105,6 +107,7 @@ def run_pipeline(model, rank, world, dev, *, mb_rows, n_mb, head_split, prompts,
     hslice = vocab_slices(model.vocab, world)[rank] if pipe.head_split else None
     last_head = pipe.is_last and not pipe.head_split
     w_b = 2 if dtype == "bf16" else 4
+    kv_b = config.kv_bytes_per_element(model, True) if kv_int8 else w_b
     st = pipe.ex.stage if hasattr(pipe.ex, "stage") else None
     out = []
     for i, P in enumerate(prompts):
@@ -144,7 +147,7 @@ def run_pipeline(model, rank, world, dev, *, mb_rows, n_mb, head_split, prompts,
             st.profile_enable(0)
             dist.barrier()
         ctx_mid = P + W + K / 2
-        step_bytes = stage_step_bytes(model, lb, le, mb_rows, ctx_mid, pipe.is_first, last_head, hslice, w_b, w_b)
+        step_bytes = stage_step_bytes(model, lb, le, mb_rows, ctx_mid, pipe.is_first, last_head, hslice, w_b, kv_b)
         pre_flops = config.prefill_flops(model, le - lb, mb_rows * n_mb, P, False)
         mine = {"rank": rank, "layers": [lb, le], "head_slice": list(hslice) if hslice else None,
                 "algo_bytes_per_forward": step_bytes, "achieved_GBps": n_mb * step_bytes / (dt / K) / 1e9,

@@ -63,6 +63,11 @@ class RunConfig:
     seed: int = 0                 # weight generator seed
     head_split: bool = True       # vocabulary-parallel lm_head ring when world > 1
     prefill: bool = True          # an admitted sample's prompt as one prefill pass of its row (else a token a round)
+    kv: str = "bf16"              # KV cache storage: "bf16", or "int8" (BS_FLAG_INT8_KV: about half the cache bytes)
+
+    def __post_init__(self):
+        if self.kv not in ("bf16", "int8"):
+            raise ValueError(f"kv must be 'bf16' or 'int8' (got {self.kv!r})")
 
 
 def synthetic_prompts(cfg: RunConfig, vocab):
@@ -148,7 +153,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     max_seq = -(-max(lens) // mb) if pf else 1  # a prefill pass of one row fits a micro-batch's hop buffers
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + cfg.max_length + 1, max_seq=max_seq, seed=cfg.seed,
-                                head_split=cfg.head_split, executor_factory=executor_factory)
+                                head_split=cfg.head_split, executor_factory=executor_factory,
+                                kv_int8=cfg.kv == "int8")
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "rounds": T, "prefill": pf})
     cuda = device.type == "cuda"
@@ -227,7 +233,7 @@ def _classify_run(cfg, model, rank, world, device, prompts, lens, executor_facto
     passes = classify_batches(lens, rows)
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + 1, max_seq=max(lens), seed=cfg.seed, head_split=False,
-                                executor_factory=executor_factory, n_labels=cfg.n_labels)
+                                executor_factory=executor_factory, n_labels=cfg.n_labels, kv_int8=cfg.kv == "int8")
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "passes": len(passes),
                     "task": "classification", "n_labels": cfg.n_labels})

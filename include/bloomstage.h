@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BS_ABI_VERSION 3
+#define BS_ABI_VERSION 4
 
 typedef enum {
   BS_OK = 0,
@@ -78,6 +78,24 @@ typedef enum {
  * desc->n_labels in [1, 64] (the reference reads 2).  The stage holds word_embeddings only if it is also first;
  * no head slice, no top-k sampling. */
 #define BS_FLAG_CLASSIFIER 2
+/* desc->flags.  BS_FLAG_INT8_KV (bf16 stages; BS_ERR_INVALID on an fp32 stage; head_dim a multiple of 16, else
+ * BS_ERR_UNSUPPORTED): the KV cache holds int8 codes with one fp32 scale per (position, head) vector.  Orthogonal
+ * to BS_FLAG_INT8_WEIGHTS and BS_FLAG_CLASSIFIER.
+ *   Storage: codes [layer][K|V][slot][head][pos][hd] int8, scales [layer][K|V][slot][head][pos] fp32, both zero at
+ *   init and after bs_reset_kv (a zero scale is finite: a masked position contributes exactly 0).
+ *   Rule, per vector x of hd bf16 values (the BS_FLAG_INT8_WEIGHTS arithmetic): amax = max|x|,
+ *   scale = amax > 0 ? amax / 127.f : 1.f (IEEE fp32 division), q = clamp(rintf(x / scale), -127, 127); the
+ *   dequantised value is (float)q * scale (fp32 product).
+ *   A call attends its own new positions at bf16 (the values its QKV epilogue produced) and every earlier cached
+ *   position through the int8 cache, for seq == 1 and seq > 1 alike: a prompt prefilled in one call sees no
+ *   quantisation.  A call with seq > 1 on rows that hold cached positions attends them as bf16((float)q * scale)
+ *   (the prefill attention reads a bf16 staging copy); seq == 1 reads the codes and applies the fp32 scales.
+ *   Staging: two bf16 buffers (K, V) of cap * hidden elements, cap = max(max_tokens as resolved, max_ctx), shared
+ *   by the layers and counted under workspace_bytes.  A call with seq > 1 needs
+ *   batch * (max past_len + seq) <= cap (BS_ERR_UNSUPPORTED otherwise; one row always fits).
+ *   bs_read_kv returns the dequantised fp32 values; bs_stage_info reports
+ *   kv_bytes = layers * 2 * max_batch * n_head * max_ctx * (head_dim + 4). */
+#define BS_FLAG_INT8_KV 4
 
 typedef struct bs_stage_desc {
   /* model (HF BloomConfig fields) */

@@ -3,7 +3,9 @@
 Each row: one full model as one stage (the per-stage kernels are the same ones a pipeline stage
 runs), prefill `prompt` tokens, then time `steps` graph-replayed decode steps.  Reports tokens/s,
 ms/step and the stage's algorithmic HBM bytes/step (BASELINE.md formula) / step time.
-    python tools/bench_matrix.py [--quick]
+    python tools/bench_matrix.py [--quick] [--kv=int8 | --kv=bf16,int8 --reps=3] [--only=model:batch,...]
+--kv=int8 builds the stage with the int8 KV cache (BS_FLAG_INT8_KV) and counts its bytes in algo_GB_per_step;
+--kv=bf16,int8 alternates the two caches per configuration, --reps times each.
 """
 import json
 import os
@@ -27,10 +29,10 @@ CONFIGS = [  # (model, batch, prompt, steps)
 ]
 
 
-def run(name, B, P, K, W=4):
+def run(name, B, P, K, W=4, kv_int8=False):
     m = config.get(name)
     st = Stage(m.hidden, m.n_head, m.n_layer, m.vocab, 0, m.n_layer, dtype="bf16", max_batch=B,
-               max_ctx=P + W + K + 1, max_tokens=max(B * P, B), seed=0)
+               max_ctx=P + W + K + 1, max_tokens=max(B * P, B), seed=0, kv_int8=kv_int8)
     cs = torch.cuda.Stream()
     with torch.cuda.stream(cs):
         ids = torch.from_numpy(prompt_ids(1234, B, P, m.vocab)).cuda()
@@ -53,9 +55,11 @@ def run(name, B, P, K, W=4):
         dt = time.perf_counter() - t0
     st.close()
     ctx = P + W + K / 2
-    byts = config.decode_step_bytes(m, m.n_layer, B, ctx, True, True)
+    byts = config.decode_step_bytes(m, m.n_layer, B, ctx, True, True,
+                                    kv_bytes=config.kv_bytes_per_element(m, kv_int8))
     ms = dt * 1e3 / K
-    return {"model": name, "batch": B, "prompt": P, "ctx_mid": ctx, "tokens_per_s": B * K / dt, "ms_per_step": ms,
+    return {"model": name, "kv": "int8" if kv_int8 else "bf16", "batch": B, "prompt": P, "ctx_mid": ctx,
+            "tokens_per_s": B * K / dt, "ms_per_step": ms,
             "algo_GB_per_step": byts / 1e9, "hbm_GBps": byts / (ms * 1e-3) / 1e9,
             "hbm_frac": byts / (ms * 1e-3) / 1e9 / HBM_PEAK, "prefill_ms": tp * 1e3,
             "prefill_TFLOPs": config.prefill_flops(m, m.n_layer, B, P, True) / tp / 1e12}
@@ -71,5 +75,12 @@ if __name__ == "__main__":
     if only:
         keep = {tuple(x.split(":")) for x in only[0].split(",")}
         cfgs = [c for c in cfgs if (c[0], str(c[1])) in keep]
+    # --kv=int8, or --kv=bf16,int8 --reps=3: the two caches alternate per configuration (an A/B inside one process)
+    kv = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--kv=")] or ["bf16"])[0].split(",")
+    if any(k not in ("bf16", "int8") for k in kv):
+        sys.exit(f"--kv takes bf16 and/or int8 (got {','.join(kv)})")
+    reps = int(([a.split("=", 1)[1] for a in sys.argv if a.startswith("--reps=")] or ["1"])[0])
     for c in cfgs:
-        print(json.dumps(run(*c)), flush=True)
+        for rep in range(reps):
+            for k in kv:
+                print(json.dumps({**run(*c, kv_int8=k == "int8"), "rep": rep}), flush=True)
