@@ -207,3 +207,15 @@ void launch_linear_q8_ln(const float* x, int row_stride, int row_offset, const v
 // LayerNorm of M fp32 rows -> bf16 (register-resident one-block-per-row kernel when K <= 4096).
 void launch_ln_rows(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta, float eps,
                     void* out_bf16, int M, int K, hipStream_t s);
+
+// ---- Teacher-forced scoring head (bf16, K % 32 == 0, V % 16 == 0; head_score.hip) ----
+// The tied lm_head W [V][K] against xn [M][K] fused with a log-softmax: per position the first index of the largest
+// logit -> top_ids[m] and {logit[target] - lse (0 without a target), logit[top] - lse, lse} -> scores[m][3] (either
+// output may be null; targets null or outside [0, V): no target).  No logit is stored: the GEMM blocks keep running
+// statistics over their run of vocabulary tiles and leave head_score_partial_bytes(M, V, cus) bytes of partials in
+// `parts`, folded per position in a fixed order by the second kernel, which also does past_adv[b] += seq for b < B
+// (the pass's last kernel).  cus: CUs of the device (sizes the vocabulary splits).
+int head_score_splits(int M, int V, int cus);
+size_t head_score_partial_bytes(int M, int V, int cus);
+void launch_head_score(const void* xn, const void* W, const int* targets, int M, int V, int K, int cus, void* parts,
+                       int* top_ids, float* scores, int* past_adv, int B, int seq, hipStream_t s);

@@ -181,7 +181,22 @@ struct bs_stage {
   HeadScreen hs{};
   int hs_on = 0;         // bs_set_head_screen; starts on where the shadow copy exists (and BS_HEAD_SCREEN is not 0)
   int hs_last_rows = 0;  // rows of the last forward if its tail ran screened, else 0 (bs_read_head_screen)
-  int cus = 0;           // CUs of the device (grids of the screened tail)
+  int cus = 0;           // CUs of the device (grids of the screened tail and of the scoring head)
+  // bs_forward_score (head_score.hip): the per-split partials of the scoring head and the host-I/O staging of
+  // targets / top_ids / scores, one allocation made by the first scoring call (null: the stage never scored)
+  char* sc_base = nullptr;
+  size_t sc_bytes = 0;
+  void* sc_parts = nullptr;
+  int* sc_targets = nullptr;  // [max_tokens]
+  int* sc_top = nullptr;      // [max_tokens]
+  float* sc_scores = nullptr; // [max_tokens][3]
+};
+
+// What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
+struct ScoreIO {
+  const int32_t* targets;
+  int32_t* top_ids;
+  float* scores;
 };
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -306,6 +321,7 @@ static void free_stage(bs_stage* s) {
   if (s->sample_logits) hipFree(s->sample_logits);
   if (s->wtmp) hipFree(s->wtmp);
   if (s->hs_base) hipFree(s->hs_base);
+  if (s->sc_base) hipFree(s->sc_base);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
@@ -731,8 +747,8 @@ extern "C" int bs_stage_info(const bs_stage* s, bs_stage_desc* d, uint64_t* wb, 
   if (d) *d = s->d;
   if (wb) *wb = s->wbytes;
   if (kvb) *kvb = s->kvbytes;
-  // the head-screening shadow copy and the int8 KV staging count as workspace
-  if (wsb) *wsb = s->wsbytes + s->hs_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
+  // the head-screening shadow copy, the int8 KV staging and the scoring buffers count as workspace
+  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
   return BS_OK;
 }
 
@@ -1155,8 +1171,9 @@ static int logits_staging(bs_stage* s, size_t bytes, hipStream_t st, float** out
 
 // Enqueue one forward on `st`.  The kernels read each row's past_len from past_dev (device [B],
 // written ahead of the forward or of the graph replay); `pasts` is the host copy (profiling bytes).
+// sc (bs_forward_score): the tail scores every position instead of picking each row's next token.
 static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, hipStream_t st,
-                           const int* past_dev, const std::vector<int>& pasts) {
+                           const int* past_dev, const std::vector<int>& pasts, const ScoreIO* sc = nullptr) {
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot, past = pasts[0];
   double ctx_sum = 0.0;
@@ -1284,6 +1301,25 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
       HIP_TRY(hipMemcpyAsync(out, s->tok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
       if (dev_logits)
         HIP_TRY(hipMemcpyAsync(logits, dev_logits, (size_t)B * s->n_labels * 4, hipMemcpyDeviceToHost, st));
+    }
+  } else if (d.is_last && sc) {
+    // teacher-forced scoring: ln_f of all M positions -> xn, then the tied lm_head fused with a log-softmax
+    // (head_score.hip); its merge kernel is the pass's last and advances past_dev by S
+    const int* tg = sc->targets;
+    if (host_io && tg) {
+      HIP_TRY(hipMemcpyAsync(s->sc_targets, tg, (size_t)M * 4, hipMemcpyHostToDevice, st));
+      tg = s->sc_targets;
+    }
+    int* top = sc->top_ids ? (host_io ? s->sc_top : sc->top_ids) : nullptr;
+    float* scr = sc->scores ? (host_io ? s->sc_scores : sc->scores) : nullptr;
+    launch_layernorm(s->bf16, cur, nullptr, 1, 0, s->lnf_g, s->lnf_b, s->xn, 0, M, h, d.ln_eps, st);
+    {
+      ProfScope p(s, st, 2, 2.0 * M * V * h);
+      launch_head_score(s->xn, s->wemb, tg, M, V, h, s->cus, s->sc_parts, top, scr, s->past_dev, B, S, st);
+    }
+    if (host_io) {
+      if (top) HIP_TRY(hipMemcpyAsync(sc->top_ids, top, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+      if (scr) HIP_TRY(hipMemcpyAsync(sc->scores, scr, (size_t)M * 12, hipMemcpyDeviceToHost, st));
     }
   } else if (d.is_last) {
     // ln_f on each row's last position, tied lm_head, token pick (greedy argmax or top-k sample)
@@ -1419,7 +1455,10 @@ extern "C" int bs_read_head_screen(bs_stage* s, int32_t row, float* hilo, float*
   return BS_OK;
 }
 
-extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, void* stream) {
+// bs_forward and bs_forward_score (sc non-null): argument checks, the rows' positions on the device, the enqueue
+// (captured or eager) and the bookkeeping of what the pass's last kernel left in past_dev.
+static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, const ScoreIO* sc,
+                        void* stream) {
   if (!s || !step) return fail(BS_ERR_INVALID, "stage/step is NULL");
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot;
@@ -1439,7 +1478,7 @@ extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void
                                           " positions exceed the staging capacity of " +
                                           std::to_string(s->kv_stage_cap) + " (max(max_tokens, max_ctx))");
   }
-  if (!in || !out) return fail(BS_ERR_INVALID, "in/out is NULL");
+  if (!in || (!out && !sc)) return fail(BS_ERR_INVALID, "in/out is NULL");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   if (want_logits && (!d.is_last || !logits)) return fail(BS_ERR_INVALID, "logits requested on a non-last stage or NULL");
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
@@ -1460,7 +1499,7 @@ extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void
   const bool past_matches = s->past_next_valid && s->past_stream == st && (int)s->past_next.size() == B &&
                             std::equal(pasts.begin(), pasts.end(), s->past_next.begin());
   s->past_next_valid = false;  // until this forward is enqueued
-  const bool graph = S == 1 && !host_io && s->prof.cls == 0 && s->graphs_on;
+  const bool graph = S == 1 && !host_io && s->prof.cls == 0 && s->graphs_on && !sc;  // scoring is always eager
   if (graph) {
     GraphKey key{B, slot, step->flags, in, out, logits, st};
     hipGraphExec_t exec = nullptr;
@@ -1499,13 +1538,13 @@ extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void
       launch_set_past(s->past_dev, pasts.data(), B, st);
     }
     BS_TRACE("enqueue_forward (eager)");
-    int rc = enqueue_forward(s, step, in, out, logits, st, s->past_dev, pasts);
+    int rc = enqueue_forward(s, step, in, out, logits, st, s->past_dev, pasts, sc);
     if (rc != BS_OK) return rc;
   }
   BS_TRACE("hipGetLastError");
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
-  s->hs_last_rows = head_screened(s, B, want_logits) ? B : 0;
+  s->hs_last_rows = !sc && head_screened(s, B, want_logits) ? B : 0;
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)
     s->past_next.assign(pasts.begin(), pasts.end());
     for (int& p : s->past_next) p += S;
@@ -1518,4 +1557,41 @@ extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void
   }
   BS_TRACE("done");
   return BS_OK;
+}
+
+extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, void* stream) {
+  return forward_impl(s, step, in, out, logits, nullptr, stream);
+}
+
+extern "C" int bs_forward_score(bs_stage* s, const bs_step* step, const void* in, const int32_t* targets,
+                                int32_t* top_ids, float* scores, void* stream) {
+  if (!s || !step) return fail(BS_ERR_INVALID, "stage/step is NULL");
+  const bs_stage_desc& d = s->d;
+  if (!d.is_last || s->n_labels || !s->wemb)
+    return fail(BS_ERR_STATE, "scoring needs the last stage of a generation model (ln_f + the whole lm_head)");
+  if (!s->bf16) return fail(BS_ERR_UNSUPPORTED, "scoring needs a BFLOAT16 stage");
+  if (step->flags & BS_STEP_LOGITS) return fail(BS_ERR_INVALID, "BS_STEP_LOGITS is not valid for a scoring pass");
+  if (!top_ids && !scores) return fail(BS_ERR_INVALID, "top_ids and scores are both NULL");
+  HIP_TRY(hipSetDevice(d.device));
+  if (!s->sc_base) {  // first scoring call: partials for the largest pass + host-I/O staging
+    if (s->cus <= 0) HIP_TRY(hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, d.device));
+    const size_t T = d.max_tokens;
+    size_t pb = 0;
+    for (size_t m = 128; m < T + 128; m += 128)  // the splits shrink as the row tiles grow
+      pb = std::max(pb, head_score_partial_bytes((int)std::min(m, T), d.vocab, s->cus));
+    const size_t sizes[4] = {pb, T * 4, T * 4, T * 12};
+    size_t so[4], off = 0;
+    for (int i = 0; i < 4; i++) { so[i] = off; off = align_up(off + sizes[i], 256); }
+    if (hipMalloc((void**)&s->sc_base, off) != hipSuccess) {
+      s->sc_base = nullptr;
+      return fail(BS_ERR_OOM, "scoring buffers allocation failed (" + std::to_string(off) + " B)");
+    }
+    s->sc_bytes = off;
+    s->sc_parts = s->sc_base + so[0];
+    s->sc_targets = (int*)(s->sc_base + so[1]);
+    s->sc_top = (int*)(s->sc_base + so[2]);
+    s->sc_scores = (float*)(s->sc_base + so[3]);
+  }
+  const ScoreIO sc{targets, top_ids, scores};
+  return forward_impl(s, step, in, nullptr, nullptr, &sc, stream);
 }

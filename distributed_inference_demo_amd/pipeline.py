@@ -66,6 +66,15 @@ class StageExecutor:
         self._run(lambda h: self.stage.forward(inp, out, batch, seq, slot=slot, past_len=past_len, stream=h),
                   (inp, out))
 
+    def score(self, inp, targets, top_ids, scores, batch, seq, slot, past_len):
+        """Teacher-forced scoring pass of the last stage (Stage.score), ordered like forward."""
+        sh = torch.cuda.current_stream().cuda_stream
+        if sh:
+            self.stage.score(inp, targets, top_ids, scores, batch, seq, slot=slot, past_len=past_len, stream=sh)
+            return
+        self._run(lambda h: self.stage.score(inp, targets, top_ids, scores, batch, seq, slot=slot, past_len=past_len,
+                                             stream=h), (inp, targets, top_ids, scores))
+
     def head_norm(self, hidden, batch, seq, xn):
         sh = torch.cuda.current_stream().cuda_stream
         if sh:
@@ -370,6 +379,66 @@ def classify(pipe: Pipeline, prompt, prompt_len):
     if not pipe.is_first:
         return None
     return torch.cat([r[-1] for r in rec], 0)
+
+
+def score(pipe: Pipeline, prompt, prompt_len):
+    """Teacher-forced scoring (bs_forward_score): one pipeline pass of `prompt` [n_mb*mb, prompt_len] (rank 0; None
+    elsewhere) from empty KV rows; the last stage scores every position against the prompt shifted left by one
+    (-1, no target, at each row's last position).  Rank 0 returns (top_ids int32 [n_mb*mb, prompt_len], scores
+    fp32 [n_mb*mb, prompt_len, 3] = log p(next prompt token) or 0.0, log p(greedy token), logsumexp); other ranks
+    None.  Rank 0 sends each micro-batch's targets to the last rank on the token group before the pass and receives
+    the results there; a world-1 pipeline skips both hops.  The last stage must hold the whole lm_head
+    (head_split=False).  Collective: every rank calls it."""
+    if pipe.head_split:
+        raise ValueError("score needs the whole lm_head on the last stage: build the pipeline with head_split=False")
+    S, mb, n_mb, dev, last = prompt_len, pipe.mb, pipe.n_mb, pipe.dev, pipe.world - 1
+    n_el = mb * S * pipe.h
+    hop = pipe.world > 1
+    pipe.past = [0] * n_mb  # every pass scores new samples
+    tg = top = sc = None
+    if pipe.is_first:
+        tg = torch.full((n_mb * mb, S), -1, dtype=torch.int32, device=dev)
+        tg[:, :-1] = prompt[:, 1:]
+    if pipe.is_first or pipe.is_last:
+        top = torch.empty((n_mb, mb, S), dtype=torch.int32, device=dev)
+        sc = torch.empty((n_mb, mb, S, 3), dtype=torch.float32, device=dev)
+    sends, keep = [], []
+    for j in range(n_mb):
+        pipe._drain(pipe.pending[j])
+        pipe._drain(pipe.tsend[j])
+        tj = None
+        if pipe.is_first:
+            tj = tg[j * mb:(j + 1) * mb].contiguous()
+            if hop:
+                sends.append(dist.isend(tj, dst=last, group=pipe.tok_group))
+            inp = prompt[j * mb:(j + 1) * mb].contiguous()
+        if pipe.is_last and hop:  # the targets first: rank 0 sent them before its forward
+            tj = torch.empty((mb, S), dtype=torch.int32, device=dev)
+            _recv(tj, 0, pipe.tok_group)
+        if not pipe.is_first:
+            inp = pipe._view(pipe.hin, j, n_el)
+            _recv(inp, pipe.rank - 1)
+        keep.append(tj)
+        if pipe.is_last:
+            pipe.ex.score(inp, tj, top[j], sc[j], mb, S, j * mb, 0)
+            if hop:
+                sends.append(dist.isend(top[j], dst=0, group=pipe.tok_group))
+                sends.append(dist.isend(sc[j], dst=0, group=pipe.tok_group))
+        else:
+            out = pipe._view(pipe.hout, j, n_el)
+            pipe.ex.forward(inp, out, mb, S, j * mb, 0)
+            pipe.pending[j].append(dist.isend(out, dst=pipe.rank + 1))
+        pipe.past[j] = S
+    if pipe.is_first and hop:
+        for j in range(n_mb):
+            _recv(top[j], last, pipe.tok_group)
+            _recv(sc[j], last, pipe.tok_group)
+    pipe._drain(sends)
+    for j in range(n_mb):
+        pipe._drain(pipe.pending[j])
+    if not pipe.is_first:
+        return None
+    return top.view(n_mb * mb, S), sc.view(n_mb * mb, S, 3)
 
 
 def init_distributed(backend=None, timeout_s=None):

@@ -27,6 +27,9 @@ max_length == 0 is the classification task (Communication.java:591-603: one OneS
 last device's classifier tail, binaryClassify at Communication.java:532-534): the last stage holds a
 score head of `n_labels` labels (BS_FLAG_CLASSIFIER), samples of equal prompt length go through
 together, `core_pool_size` rows a pass, and rank 0 returns each sample's class id (first maximal label).
+--score is the scoring task (no counterpart in the reference): every sample's prompt is one teacher-forced pass
+(pipeline.score, bs_forward_score on the last stage), `core_pool_size` samples a pass, and rank 0 returns each
+sample's summed log-likelihood, token count and perplexity.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax instead of unseeded top-k, token ids in (no tokenizer).
 
@@ -64,6 +67,7 @@ class RunConfig:
     head_split: bool = True       # vocabulary-parallel lm_head ring when world > 1
     prefill: bool = True          # an admitted sample's prompt as one prefill pass of its row (else a token a round)
     kv: str = "bf16"              # KV cache storage: "bf16", or "int8" (BS_FLAG_INT8_KV: about half the cache bytes)
+    score: bool = False           # the scoring task: each prompt's log-likelihood and perplexity, one pass a sample
 
     def __post_init__(self):
         if self.kv not in ("bf16", "int8"):
@@ -119,6 +123,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
             t = t.to(device)
         dist.broadcast(t, src=0)
         lens = [int(v) for v in t.tolist()]
+    if cfg.score:
+        return _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.max_length == 0:
         return _classify_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     # samples in flight = n_mb micro-batches x mb rows: one micro-batch per stage keeps every stage
@@ -269,12 +275,64 @@ def _classify_run(cfg, model, rank, world, device, prompts, lens, executor_facto
     return res
 
 
+def _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say):
+    """--score: every sample's prompt is one teacher-forced pass from empty KV rows (pipeline.score), `core_pool_size`
+    samples a pass in sample order.  Ragged prompts are padded at the tail to the pass's longest (token 0, no
+    target): attention is causal, so the real positions do not see the padding.  Rank 0 returns per sample the
+    summed log-likelihood of tokens 2..n given their prefixes, their count and the perplexity exp(-sum / count)."""
+    import math
+    from .pipeline import score
+    n_mb = min(cfg.core_pool_size, world)
+    mb = -(-cfg.core_pool_size // n_mb)
+    rows = n_mb * mb
+    passes = [list(range(k, min(k + rows, cfg.num_sample))) for k in range(0, cfg.num_sample, rows)]
+    pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
+                                max_ctx=max(lens) + 1, max_seq=max(lens), seed=cfg.seed, head_split=False,
+                                executor_factory=executor_factory, kv_int8=cfg.kv == "int8")
+    say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
+                    "micro_batches": n_mb, "rows_per_micro_batch": mb, "passes": len(passes), "task": "score"})
+    cuda = device.type == "cuda"
+    if cuda:
+        torch.cuda.set_stream(torch.cuda.Stream(device))
+    if world > 1:
+        dist.barrier()
+    say(STATES[1], {"num_sample": cfg.num_sample, "task": "score"})
+    out = [None] * cfg.num_sample
+    t_start = time.perf_counter()
+    for ids in passes:
+        n = max(lens[i] for i in ids)
+        prompt = None
+        if rank == 0:  # spare rows of a short pass repeat its first sample (their scores are dropped)
+            prompt = torch.tensor([prompts[i] + [0] * (n - lens[i]) for i in ids + [ids[0]] * (rows - len(ids))],
+                                  dtype=torch.int32, device=device)
+        res = score(pipe, prompt, n)
+        if rank == 0:
+            lp = res[1][..., 0].double().cpu()
+            for r, i in enumerate(ids):
+                cnt = lens[i] - 1
+                ll = float(lp[r, :cnt].sum())  # position t scores token t + 1; the padding is not counted
+                out[i] = {"loglik": ll, "tokens": cnt, "perplexity": math.exp(-ll / cnt) if cnt else None}
+    if cuda:
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t_start
+    if world > 1:
+        dist.barrier()
+    if rank != 0:
+        return None
+    ntok = sum(lens)
+    res = {"samples": out, "task": "score", "num_sample": cfg.num_sample, "core_pool_size": cfg.core_pool_size,
+           "stages": world, "prompt_lens": lens, "passes": len(passes), "seconds": dt, "tokens_per_s": ntok / dt}
+    say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
+    say(STATES[3], {})
+    return res
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     for f in dataclasses.fields(RunConfig):
         flag = "--" + f.name.replace("_", "-")
         if f.type is bool or f.type == "bool":
-            p.add_argument(flag, type=int, default=int(f.default))
+            p.add_argument(flag, type=int, nargs="?", const=1, default=int(f.default))  # `--score` == `--score 1`
         else:
             p.add_argument(flag, type=type(f.default), default=f.default)
     p.add_argument("--prompts-file", default=None, help="JSON list of token-id lists (one per sample)")

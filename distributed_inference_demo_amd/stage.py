@@ -87,6 +87,7 @@ EXPORTS = [
     "bs_prompt_ids", "bs_read_weights", "bs_head_norm", "bs_head_slice", "bs_stream_delay", "bs_set_sampling",
     "bs_build_id", "bs_hbm_probe", "bs_mfma_probe", "bs_init_stage_file", "bs_weights_file_probe",
     "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
+    "bs_forward_score",
 ]
 
 _LIB = None
@@ -113,6 +114,7 @@ def lib():
         L.bs_init_stage_file.argtypes = [ctypes.POINTER(StageDesc), ctypes.c_char_p, ctypes.POINTER(vp)]
         L.bs_weights_file_probe.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(i32)] * 3
         L.bs_forward.argtypes = [vp, ctypes.POINTER(Step), vp, vp, vp, vp]
+        L.bs_forward_score.argtypes = [vp, ctypes.POINTER(Step), vp, vp, vp, vp, vp]
         L.bs_reset_kv.argtypes = [vp, i32]
         L.bs_read_kv.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bs_release.argtypes = [vp]
@@ -269,6 +271,41 @@ class Stage:
             for i, r in enumerate(range(slot, slot + batch)):
                 self.past[r] = pasts[i] + seq
         return out
+
+    def _advance(self, st, pasts, batch, seq, slot):
+        if pasts is None:
+            self.past[slot:slot + batch] = [st.past_len + seq] * batch
+        else:
+            for i, r in enumerate(range(slot, slot + batch)):
+                self.past[r] = pasts[i] + seq
+
+    # ---- teacher-forced scoring (bs_forward_score; last stage of a bf16 generation model)
+    def score(self, inp, targets, top_ids, scores, batch, seq, slot=0, past_len=None, stream=None):
+        """Log-probabilities and greedy ids at every position, on device pointers (stream ordered).
+        inp: forward()'s input; targets: int32 [batch][seq] (-1 = none) or None; top_ids: int32 [batch][seq] or
+        None; scores: fp32 [batch][seq][3] = (log p(target), log p(top id), logsumexp) or None.  Appends seq
+        positions to the KV rows like forward(), so a long text scores in chunks with past_len."""
+        st, pasts = self._step(batch, seq, slot, past_len, 0)
+        _check(lib().bs_forward_score(self._h, ctypes.byref(st), _ptr(inp), _ptr(targets), _ptr(top_ids),
+                                      _ptr(scores), stream))
+        self._advance(st, pasts, batch, seq, slot)
+        return top_ids, scores
+
+    def score_host(self, x, targets, batch, seq, slot=0, past_len=None):
+        """score() with numpy in and out: returns (top_ids int32 [batch][seq], scores fp32 [batch][seq][3])."""
+        if self.is_first:
+            x = np.ascontiguousarray(x, dtype=np.int32).reshape(batch, seq)
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32).reshape(batch, seq, self.hidden)
+        if targets is not None:
+            targets = np.ascontiguousarray(targets, dtype=np.int32).reshape(batch, seq)
+        top = np.empty((batch, seq), np.int32)
+        scores = np.empty((batch, seq, 3), np.float32)
+        st, pasts = self._step(batch, seq, slot, past_len, BS_STEP_HOST_IO)
+        _check(lib().bs_forward_score(self._h, ctypes.byref(st), x.ctypes.data, _ptr(targets), top.ctypes.data,
+                                      scores.ctypes.data, None))
+        self._advance(st, pasts, batch, seq, slot)
+        return top, scores
 
     def set_sampling(self, top_k=1, temperature=1.0, seed=0):
         """Tail token pick (bs_set_sampling): greedy for top_k <= 1, else seeded top-k sampling in

@@ -12,6 +12,7 @@
  *                         runInferenceWorkerResidualLastGeneration (:1368-1443, tail stage),
  *                         all of which end in inference::run_inference (inference.cpp:145-218)
  *   bs_reset_kv        <- (none: the reference has no KV cache; new sample == new slot)
+ *   bs_forward_score   <- (none: the reference has no scoring task)
  *   bs_last_error      <- (none: the reference throws C++ exceptions across JNI,
  *                         native-lib.cpp:986-988; here errors are status codes + this string)
  *   bs_forward on a BS_FLAG_CLASSIFIER stage
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define BS_ABI_VERSION 4
+#define BS_ABI_VERSION 5
 
 typedef enum {
   BS_OK = 0,
@@ -176,6 +177,28 @@ int bs_weights_file_probe(const char *path, int32_t *hidden, int32_t *n_layer, i
  * bs_set_sampling selected top-k sampling. */
 int bs_forward(bs_stage *stage, const bs_step *step, const void *in, void *out, float *logits,
                void *stream);
+
+/* Teacher-forced scoring pass (last stage of a generation model, bf16): log-probabilities and greedy ids at every
+ * position instead of a token at each row's last one -- perplexity, ranking by log-likelihood, and the verify step of
+ * speculative decoding.  `step` and `in` are bs_forward's (B rows x S new tokens, per-row past_lens; ids on a
+ * first + last stage, fp32 hidden otherwise); BS_STEP_HOST_IO covers in, targets, top_ids and scores; BS_STEP_LOGITS
+ * is BS_ERR_INVALID.  Like bs_forward it appends S positions to the KV rows, and its last kernel advances the device
+ * copy of each row's position by S, so a bs_forward (or another scoring chunk with past_len) on the same stream
+ * continues from it.  Always launched eagerly; bs_read_head_screen reports the full head afterwards.
+ *  Logits: for position (b, t), l[v] = the fp32-accumulated dot of bf16(ln_f(hidden[b][t])) with bf16 row v of the
+ *       tied lm_head (the operands of bs_forward's head); lse = log sum_v exp(l[v]).  No logit is stored.
+ *  targets: int32 [B][S], the token whose probability is wanted at that position's output; a value outside
+ *       [0, vocab) (use -1) means none; NULL = none anywhere.
+ *  top_ids: int32 [B][S], the first index of the largest l[v] (the greedy rule); may be NULL.
+ *  scores: fp32 [B][S][3] = {l[target] - lse (0.0f without a target), l[top_id] - lse, lse}; may be NULL (not
+ *       both).
+ * Results are bit-identical from run to run (no floating-point atomics, partials folded in a fixed order).
+ * BS_ERR_STATE on a classifier stage or a stage without ln_f and the whole lm_head (not last); BS_ERR_UNSUPPORTED on
+ * an fp32 stage; BS_FLAG_INT8_WEIGHTS / BS_FLAG_INT8_KV stages score (the head stays bf16).  batch * seq <=
+ * max_tokens.  The first scoring call allocates the head's per-split partials and the host-I/O staging (well under
+ * max_tokens * vocab bytes; no buffer grows with batch * seq * vocab), counted under workspace_bytes from then on. */
+int bs_forward_score(bs_stage *stage, const bs_step *step, const void *in, const int32_t *targets,
+                     int32_t *top_ids, float *scores, void *stream);
 
 /* ---- Vocabulary-parallel head (stages with a head slice, or the last stage) ----
  * Argmax keys: uint64 (order(logit) << 32) | (0xFFFFFFFF - vocab_index), where order() maps
