@@ -12,6 +12,7 @@ class BloomDims:
     vocab: int = 250880
     eps: float = 1e-5
     int8_weights: bool = False  # "-int8" model names: weight-only int8 stages (BS_FLAG_INT8_WEIGHTS)
+    mxfp4_weights: bool = False  # "-mxfp4" model names: weight-only MXFP4 stages (BS_FLAG_MXFP4_WEIGHTS)
 
     @property
     def head_dim(self):
@@ -34,14 +35,22 @@ MODELS = {
 
 def get(name: str) -> BloomDims:
     """Model by name: "bloom-560m", "560m", the reference's "bloom560m"; an "-int8" suffix
-    ("bloom560m-int8", server.py:796-799) selects the weight-only int8 variant of the same dims."""
-    int8 = name.endswith("-int8")
-    base = name[:-5] if int8 else name
+    ("bloom560m-int8", server.py:796-799) selects the weight-only int8 variant of the same dims, a "-mxfp4"
+    suffix ("bloom-7b1-mxfp4") the weight-only MXFP4 variant."""
+    int8, mxfp4 = name.endswith("-int8"), name.endswith("-mxfp4")
+    base = name[:-5] if int8 else (name[:-6] if mxfp4 else name)
     if base.startswith("bloom") and not base.startswith("bloom-") and base not in MODELS:
         base = "bloom-" + base[5:]
     key = base if base.startswith("bloom-") or base in MODELS else f"bloom-{base}"
     m = MODELS[key]
+    if mxfp4:
+        return replace(m, name=m.name + "-mxfp4", mxfp4_weights=True)
     return replace(m, name=m.name + "-int8", int8_weights=True) if int8 else m
+
+
+# HBM bytes per weight of a block matrix (qkv, dense, fc1, fc2) by storage format; MXFP4: a 4-bit code plus one
+# scale byte per block of 32 weights.
+MXFP4_BYTES_PER_WEIGHT = 0.5 + 1.0 / 32
 
 
 def kv_bytes_per_element(m: BloomDims, kv_int8: bool = False) -> float:
@@ -51,12 +60,16 @@ def kv_bytes_per_element(m: BloomDims, kv_int8: bool = False) -> float:
 
 
 def decode_step_bytes(m: BloomDims, layers: int, batch: int, ctx: int, first: bool, last: bool,
-                      w_bytes: int = 2, kv_bytes: float = 2, act_bytes: int = 4) -> float:
+                      w_bytes: float = 2, kv_bytes: float = 2, act_bytes: int = 4,
+                      matrix_bytes: float = None) -> float:
     """Algorithmic HBM bytes of one decode step of a stage (BASELINE.md / SURVEY §8d):
     sum_layers[(12h^2+13h)w + 2*B*ctx*h*k (KV read) + 2*B*h*k (KV write)]
-    + [first](B*h*w + 4h*w... emb row gather + emb LN) + [last](V*h*w + 2h*w) + 2*B*h*act."""
+    + [first](B*h*w + 4h*w... emb row gather + emb LN) + [last](V*h*w + 2h*w) + 2*B*h*act.
+    matrix_bytes (may be fractional, e.g. MXFP4_BYTES_PER_WEIGHT): bytes per weight of the four block matrices
+    (12h^2 per layer) where they are stored in another format than the rest (w_bytes); None = w_bytes."""
     h = m.hidden
-    b = layers * (m.block_params() * w_bytes + 2 * batch * ctx * h * kv_bytes + 2 * batch * h * kv_bytes)
+    mb = w_bytes if matrix_bytes is None else matrix_bytes
+    b = layers * (12 * h * h * mb + 13 * h * w_bytes + 2 * batch * ctx * h * kv_bytes + 2 * batch * h * kv_bytes)
     if first:
         b += batch * h * w_bytes + 4 * h * w_bytes
     if last:

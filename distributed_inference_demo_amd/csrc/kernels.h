@@ -204,6 +204,27 @@ bool linear_q8_ln_fused(int M, int K);
 void launch_linear_q8_ln(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
                          float eps, const int8_t* Q, const float* scale, int M, int N, int K, const Epi& ep,
                          hipStream_t s);
+// ---- Weight-only MXFP4 (bf16 stages with BS_FLAG_MXFP4_WEIGHTS; kernels.hip "Weight-only MXFP4") ----
+// W bf16 [N][K], K % 32 == 0 -> E2M1 codes Q (N * K / 2 bytes, 16-B block records) + E8M0 scales SC [N][K / 32]
+// by the rule of include/bloomstage.h.
+void launch_quantize_mx4(const void* W_bf16, uint8_t* Q, uint8_t* SC, int N, int K, hipStream_t s);
+// out bf16 [N][K] = the dequantised weights (exact in bf16).
+void launch_dequant_mx4(const uint8_t* Q, const uint8_t* SC, void* out_bf16, int N, int K, hipStream_t s);
+// Does launch_linear_mx4 run M rows of an N x K matrix straight from the fp4 codes?
+bool linear_mx4_gemv(int M, int N, int K);
+// X bf16 [M][K] x dequant(Q, SC)^T with epilogue (not EPI_ARGMAX).  linear_mx4_gemv(M, N, K): fp4 GEMV;
+// otherwise the weights are dequantised into w_scratch (bf16, N*K) and the bf16 GEMM runs on them.
+void launch_linear_mx4(const void* X, const uint8_t* Q, const uint8_t* SC, void* w_scratch, int M, int N, int K,
+                       const Epi& ep, hipStream_t s);
+// The fp4 dense GEMV on ctx = merge(split-attention partials) (M <= 2).
+bool linear_mx4_parts_supported(int M, int K, int head_dim, int nsplit);
+void launch_linear_mx4_parts(const AttnParts& p, const uint8_t* Q, const uint8_t* SC, int M, int N, int K,
+                             const Epi& ep, hipStream_t s);
+// M <= 4, K <= 4096: LayerNorm(x rows) fused into the fp4 GEMV prologue.
+bool linear_mx4_ln_fused(int M, int K);
+void launch_linear_mx4_ln(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
+                          float eps, const uint8_t* Q, const uint8_t* SC, int M, int N, int K, const Epi& ep,
+                          hipStream_t s);
 // LayerNorm of M fp32 rows -> bf16 (register-resident one-block-per-row kernel when K <= 4096).
 void launch_ln_rows(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta, float eps,
                     void* out_bf16, int M, int K, hipStream_t s);

@@ -3529,6 +3529,336 @@ void launch_linear_q8(const void* X, const int8_t* Q, const float* scale, void* 
 }
 
 // ------------------------------------------------------------------------------------
+// Weight-only MXFP4 (BS_FLAG_MXFP4_WEIGHTS; rule in include/bloomstage.h): the four
+// block matrices of a bf16 stage as OCP E2M1 codes with one E8M0 scale byte per 32 consecutive k of a row.
+// Layout, chosen for the decode stream: codes [N][K/32] records of 16 B, scales [N][K/32] bytes.  The record of
+// block b of a row holds its four 8-weight groups rotated: dword d carries k = 32 b + 8 ((d + (b >> 2)) & 3) + i,
+// i = 0..7, two codes per byte, the even i in the low nibble.  A GEMV lane owns block b = lane + 64 * step, so
+// its rotation (lane >> 2) & 3 is fixed, and the 16-B activation reads of one dword index fall on 64 different
+// banks within each ds_read_b128 lane group (linear bf16 rows in LDS, 64 B per lane, are 4-way otherwise).
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t mx4_code(float w, float inv) {
+  const float r = fabsf(w) * inv;  // exact: inv is a power of two
+  const uint32_t idx = (uint32_t)(r > 0.25f) + (uint32_t)(r >= 0.75f) + (uint32_t)(r > 1.25f) + (uint32_t)(r >= 1.75f) +
+                       (uint32_t)(r > 2.5f) + (uint32_t)(r >= 3.5f) + (uint32_t)(r > 5.0f);
+  return idx | ((__float_as_uint(w) >> 28) & 8u);
+}
+
+// One thread per block of 32 weights.
+__global__ __launch_bounds__(256) void quantize_mx4_kernel(const bf16* __restrict__ W, uint8_t* __restrict__ Q,
+                                                           uint8_t* __restrict__ SC, size_t nblocks, int nb) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= nblocks) return;
+  const int b = (int)(t % nb);
+  float w[32];
+#pragma unroll
+  for (int j = 0; j < 4; j++) load8(W + t * 32 + 8 * j, w + 8 * j);
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; j++) amax = fmaxf(amax, fabsf(w[j]));
+  const bool zero = !(amax >= 0x1p-100f);
+  const uint32_t E = zero ? 127u : (__float_as_uint(amax) >> 23) - 2u;
+  const float inv = zero ? 0.f : __uint_as_float((254u - E) << 23);  // 2^(127 - E)
+  const int rot = (b >> 2) & 3;
+  u32x4v rec = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) v |= mx4_code(w[8 * g + i], inv) << (4 * i);
+    const int d = (g - rot) & 3;
+    rec[0] = d == 0 ? v : rec[0]; rec[1] = d == 1 ? v : rec[1]; rec[2] = d == 2 ? v : rec[2]; rec[3] = d == 3 ? v : rec[3];
+  }
+  *reinterpret_cast<u32x4v*>(Q + t * 16) = rec;
+  SC[t] = (uint8_t)E;
+}
+
+// out bf16 [N][K] = the dequantised weights (exact), one thread per dword of codes: the operand of the bf16 GEMM.
+__global__ __launch_bounds__(256) void dequant_mx4_kernel(const uint8_t* __restrict__ Q, const uint8_t* __restrict__ SC,
+                                                          bf16* __restrict__ out, size_t ndw, int nb) {
+  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < ndw; t += (size_t)gridDim.x * 256) {
+    const size_t blk = t >> 2;
+    const int b = (int)(blk % nb), d = (int)(t & 3), g = (d + (b >> 2)) & 3;
+    const uint32_t v = reinterpret_cast<const uint32_t*>(Q)[t];
+    const float half_x = __uint_as_float(((uint32_t)SC[blk] - 1u) << 23);  // 2^(E - 128); E >= 25
+    u16x8 o;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const uint32_t c = (v >> (4 * i)) & 15u;
+      const float mag = (float)((0xC8643210u >> (4 * (c & 7u))) & 15u) * half_x;  // twice the grid value, times X / 2
+      o[i] = __builtin_bit_cast(unsigned short, (bf16)((c & 8u) ? -mag : mag));
+    }
+    *reinterpret_cast<u16x8*>(out + blk * 32 + 8 * g) = o;
+  }
+}
+
+void launch_quantize_mx4(const void* W_bf16, uint8_t* Q, uint8_t* SC, int N, int K, hipStream_t s) {
+  const size_t nblocks = (size_t)N * (K / 32);
+  if (nblocks) quantize_mx4_kernel<<<(unsigned)((nblocks + 255) / 256), 256, 0, s>>>((const bf16*)W_bf16, Q, SC, nblocks, K / 32);
+}
+
+void launch_dequant_mx4(const uint8_t* Q, const uint8_t* SC, void* out_bf16, int N, int K, hipStream_t s) {
+  const size_t ndw = (size_t)N * K / 8;
+  const int blocks = (int)std::min<size_t>((ndw + 255) / 256, 8192);
+  if (ndw) dequant_mx4_kernel<<<blocks, 256, 0, s>>>(Q, SC, (bf16*)out_bf16, ndw, K / 32);
+}
+
+// Decode GEMV on MXFP4 weights, M <= MM <= 8 rows (gemv_q8_body's structure).  A wave owns R weight rows; per step
+// a lane streams one block record of each of its rows (16 B, non-temporal: 32 codes) and its scale byte, converts a
+// byte of two codes straight to two scaled bf16 values (v_cvt_scalef32_pk_bf16_fp4, the block scale is the
+// instruction's operand) and multiplies them into the fp32 sums of every row m with v_dot2c_f32_bf16: one
+// conversion and M dot products per weight pair.  The bf16 activations come from LDS (LayerNorm / split-attention
+// merge prologues, or plain X staged once per block) or from L2.  Lanes past the row's last block (K / 32 is not a
+// multiple of 64) load its last record again and skip the arithmetic.  DPP wave reduction, the usual epilogue.
+template <int R, int MM, bool LN, int KIND, bool XL, int UQ, bool PARTS>
+__device__ __forceinline__ void gemv_mx4_body(const uint8_t* __restrict__ Q, const uint8_t* __restrict__ SC,
+                                              const bf16* __restrict__ Xg, const LnArgs& ln, const AttnParts& pa,
+                                              int M, int N, int K, const Epi& ep) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const int lane = threadIdx.x & 63, nb = K >> 5;
+  const int n0 = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * R;  // waves past N: row N-1, no store
+  float acc[R][MM];
+#pragma unroll
+  for (int r = 0; r < R; r++)
+#pragma unroll
+    for (int m = 0; m < MM; m++) acc[r][m] = 0.f;
+  const uint8_t* qr[R];
+  const uint8_t* sr[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const size_t row = (size_t)min(n0 + r, N - 1);
+    qr[r] = Q + row * nb * 16;
+    sr[r] = SC + row * nb;
+  }
+  // UQ steps of every row in flight; the loads are unconditional (clamped to the row's last block)
+  u32x4 wv[UQ][R];
+  uint8_t sv[UQ][R];
+  auto load = [&](int u, int blk) {
+    const int b = min(blk, nb - 1);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      wv[u][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(qr[r] + (size_t)b * 16));
+      sv[u][r] = sr[r][b];
+    }
+  };
+  // prologue operands go out before the weights (loads return in order), as in gemv_q8_body
+  const int kq = K >> 2, ngroups = M * kq;
+  PartsRegs pr[1];
+  auto pld1 = [](const float* p, size_t i) { return p[i]; };
+  auto pld4 = [](const float* p, size_t i) { return *reinterpret_cast<const float4*>(p + i); };
+  if constexpr (PARTS) {
+    const int g = min((int)threadIdx.x, ngroups - 1);
+    attn_parts_load(pa, g / kq, (g % kq) * 4, pld1, pld4, pr[0]);
+  }
+  float4 xv[LN ? MM : 1][4];
+  float cc[LN ? MM : 1];
+  uint2 gb[4][2];
+  if constexpr (LN) {
+    if (threadIdx.x < 256) ln_rows_load<MM>(ln, M, K, xv, cc, gb);
+  }
+  constexpr int XP = XL ? 4 : 1;
+  u16x8 xpre[XP];
+  if constexpr (XL) {
+#pragma unroll
+    for (int j = 0; j < XP; j++) {
+      const int i = min((int)threadIdx.x + j * (int)blockDim.x, M * K / 8 - 1);
+      xpre[j] = reinterpret_cast<const u16x8*>(Xg)[i];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < UQ; u++) load(u, lane + 64 * u);
+  extern __shared__ __align__(16) unsigned char mx4_lds[];
+  const bf16* X = Xg;
+  if constexpr (LN) {
+    __shared__ float scratch[64];
+    ln_rows_finish<MM>(ln, M, K, xv, cc, gb, reinterpret_cast<bf16*>(mx4_lds), scratch);
+    X = reinterpret_cast<const bf16*>(mx4_lds);
+  } else if constexpr (PARTS) {  // merged context rows (bf16, the attn_decode_kernel rounding) to LDS
+    bf16* xl = reinterpret_cast<bf16*>(mx4_lds);
+    auto put = [&](int g, const PartsRegs& rr) {
+      float o[4];
+      attn_parts_combine(pa.nsplit, rr, o);
+      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+      bf16x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; j++) v[j] = (bf16)o[j];
+      *reinterpret_cast<bf16x4*>(xl + (size_t)(g / kq) * K + (g % kq) * 4) = v;
+    };
+    if ((int)threadIdx.x < ngroups) put(threadIdx.x, pr[0]);
+    for (int g = threadIdx.x + blockDim.x; g < ngroups; g += blockDim.x) {
+      PartsRegs rr;
+      attn_parts_load(pa, g / kq, (g % kq) * 4, pld1, pld4, rr);
+      put(g, rr);
+    }
+    __syncthreads();
+    X = xl;
+  } else if constexpr (XL) {  // plain X staged once per block in LDS
+    const int n16 = M * K / 8;
+#pragma unroll
+    for (int j = 0; j < XP; j++) {
+      const int i = threadIdx.x + j * blockDim.x;
+      if (i < n16) reinterpret_cast<u16x8*>(mx4_lds)[i] = xpre[j];
+    }
+    for (int i = threadIdx.x + XP * blockDim.x; i < n16; i += blockDim.x)
+      reinterpret_cast<u16x8*>(mx4_lds)[i] = reinterpret_cast<const u16x8*>(Xg)[i];
+    __syncthreads();
+    X = reinterpret_cast<const bf16*>(mx4_lds);
+  }
+  const int rot = (lane >> 2) & 3;
+  for (int sb = 0; sb < nb; sb += 64 * UQ) {
+    const bool more = sb + 64 * UQ < nb;
+#pragma unroll
+    for (int u = 0; u < UQ; u++) {
+      if (sb + 64 * u >= nb) continue;  // wave-uniform
+      const int blk = sb + 64 * u + lane;
+      u32x4 cur[R];
+      float scf[R];
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        cur[r] = wv[u][r];
+        scf[r] = __uint_as_float((uint32_t)sv[u][r] << 23);  // 2^(E - 127)
+      }
+      if (more) load(u, blk + 64 * UQ);  // step u of the next round replaces it in flight
+      if (blk < nb) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+          bf16x2 wq[R][4];
+#pragma unroll
+          for (int r = 0; r < R; r++) {
+            wq[r][0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cur[r][d], scf[r], 0);
+            wq[r][1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cur[r][d], scf[r], 1);
+            wq[r][2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cur[r][d], scf[r], 2);
+            wq[r][3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cur[r][d], scf[r], 3);
+          }
+          const int k = blk * 32 + ((d + rot) & 3) * 8;
+#pragma unroll
+          for (int m = 0; m < MM; m++) {
+            if (m == 0 || m < M) {  // M >= 1: row 0 takes no branch, so its four reads go out together
+              const u32x4 xa = *reinterpret_cast<const u32x4*>(X + (size_t)m * K + k);
+#pragma unroll
+              for (int i = 0; i < 4; i++) {
+                const uint32_t xi = xa[i];  // a scalar copy: __builtin_bit_cast of a vector element reads element 0
+                const bf16x2 xp = __builtin_bit_cast(bf16x2, xi);
+#pragma unroll
+                for (int r = 0; r < R; r++) acc[r][m] = __builtin_amdgcn_fdot2_f32_bf16(wq[r][i], xp, acc[r][m], false);
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  float mine = 0.f;
+#pragma unroll
+  for (int r = 0; r < R; r++)
+#pragma unroll
+    for (int m = 0; m < MM; m++) {
+      if (m < M) {
+        const float t = wave_sum(acc[r][m]);
+        if (lane == r * MM + m) mine = t;
+      }
+    }
+  const int r = lane / MM, m = lane - r * MM;
+  if (lane < R * MM && m < M && n0 + r < N) epi_store<bf16, KIND>(ep, m, n0 + r, mine);
+}
+
+template <int R, int MM, bool LN, bool XL, int UQ, bool PARTS>
+__global__ __launch_bounds__(256) void gemv_mx4_kernel(const uint8_t* __restrict__ Q, const uint8_t* __restrict__ SC,
+                                                       const bf16* __restrict__ X, LnArgs ln, AttnParts pa, int M,
+                                                       int N, int K, Epi ep) {
+  epi_dispatch(ep.kind, [&](auto kc) {
+    if constexpr (decltype(kc)::value != EPI_ARGMAX)
+      gemv_mx4_body<R, MM, LN, decltype(kc)::value, XL, UQ, PARTS>(Q, SC, X, ln, pa, M, N, K, ep);
+  });
+}
+
+// Plain X rows are staged in LDS up to this size (5 blocks of 4 waves per CU keep their 32 KB); beyond it the
+// lanes read them from L2.
+constexpr size_t kMx4XlBytes = 32768;
+
+template <int R, int MM, bool LN = false, bool PARTS = false>
+static void gemv_mx4_launch(const uint8_t* Q, const uint8_t* SC, const bf16* X, const LnArgs& ln, int M, int N,
+                            int K, const Epi& ep, hipStream_t s, const AttnParts& pa = AttnParts{}) {
+  const size_t xbytes = (size_t)M * K * sizeof(bf16);
+  const int blocks = (N + 4 * R - 1) / (4 * R);
+  // steps (64 blocks = 2048 k) of every row in flight: the whole row up to 4 steps for matrices up to 12 M weights,
+  // where latency decides; one step beyond, where the stream is bandwidth-bound (gemv_q8_launch's measured policy)
+  const int steps = (K / 32 + 63) / 64;
+  const int uq = (size_t)N * K > (12u << 20) ? 1 : (steps <= 1 ? 1 : steps <= 2 ? 2 : 4);
+  auto go = [&](auto xl, auto uc) {
+    constexpr bool XL = decltype(xl)::value != 0;
+    constexpr int UQ = decltype(uc)::value;
+    const size_t shm = (LN || PARTS || XL) ? xbytes : 0;
+    gemv_mx4_kernel<R, MM, LN, XL, UQ, PARTS><<<blocks, 256, shm, s>>>(Q, SC, X, ln, pa, M, N, K, ep);
+  };
+  auto gu = [&](auto xl) {
+    if (uq == 1) go(xl, EpiKindC<1>{});
+    else if (uq == 2) go(xl, EpiKindC<2>{});
+    else go(xl, EpiKindC<4>{});
+  };
+  if constexpr (LN || PARTS) {
+    gu(EpiKindC<0>{});
+  } else {
+    if (xbytes <= kMx4XlBytes) gu(EpiKindC<1>{});
+    else gu(EpiKindC<0>{});
+  }
+}
+
+// Which M stream the fp4 codes, measured against the dequant + bf16 route (profiles/mxfp4_passes_ab.txt, DESIGN.md
+// section 5e): up to 4 rows always; 5..8 rows where the model is at most 2048 wide (min(N, K) = hidden for all four
+// matrices) -- the 8-row instance re-reads 8 activation rows per weight row, from LDS on narrow models (+19..30 %
+// at h 1024 / 1536) but from L2 on wide ones (-14 % at h 2560 / 4096); above 8 rows never (passes of 8 rows lose at
+// every width, 1.3x at 16 rows to 3.7x at 32).
+bool linear_mx4_gemv(int M, int N, int K) {
+  return M >= 1 && K % 32 == 0 && (M <= 4 || (M <= 8 && std::min(N, K) <= 2048));
+}
+
+bool linear_mx4_ln_fused(int M, int K) { return M >= 1 && M <= 4 && K % 32 == 0 && K <= 4096; }
+
+void launch_linear_mx4_ln(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
+                          float eps, const uint8_t* Q, const uint8_t* SC, int M, int N, int K, const Epi& ep,
+                          hipStream_t s) {
+  Epi e = ep;
+  e.col_scale = nullptr;
+  const LnArgs ln{x, row_stride, row_offset, (const bf16*)gamma, (const bf16*)beta, eps};
+  if (M <= 1) gemv_mx4_launch<2, 1, true>(Q, SC, nullptr, ln, M, N, K, e, s);
+  else if (M <= 2) gemv_mx4_launch<2, 2, true>(Q, SC, nullptr, ln, M, N, K, e, s);
+  else gemv_mx4_launch<2, 4, true>(Q, SC, nullptr, ln, M, N, K, e, s);
+}
+
+bool linear_mx4_parts_supported(int M, int K, int head_dim, int nsplit) {
+  return M >= 1 && M <= 2 && K % 32 == 0 && K <= 4096 && head_dim % 4 == 0 && nsplit >= 2 && nsplit <= kPartsMaxSplit;
+}
+
+void launch_linear_mx4_parts(const AttnParts& p, const uint8_t* Q, const uint8_t* SC, int M, int N, int K,
+                             const Epi& ep, hipStream_t s) {
+  Epi e = ep;
+  e.col_scale = nullptr;
+  if (M <= 1) gemv_mx4_launch<2, 1, false, true>(Q, SC, nullptr, LnArgs{}, M, N, K, e, s, p);
+  else gemv_mx4_launch<2, 2, false, true>(Q, SC, nullptr, LnArgs{}, M, N, K, e, s, p);
+}
+
+void launch_linear_mx4(const void* X, const uint8_t* Q, const uint8_t* SC, void* w_scratch, int M, int N, int K,
+                       const Epi& ep, hipStream_t s) {
+  if (M <= 0) return;
+  if (ep.kind == EPI_ARGMAX) abort();  // the tied lm_head stays bf16
+  const bf16* x = (const bf16*)X;
+  Epi e = ep;
+  e.col_scale = nullptr;
+  if (linear_mx4_gemv(M, N, K)) {
+    const LnArgs ln{};
+    if (M <= 1) gemv_mx4_launch<2, 1>(Q, SC, x, ln, M, N, K, e, s);
+    else if (M <= 2) gemv_mx4_launch<2, 2>(Q, SC, x, ln, M, N, K, e, s);
+    else if (M <= 4) gemv_mx4_launch<2, 4>(Q, SC, x, ln, M, N, K, e, s);
+    else gemv_mx4_launch<1, 8>(Q, SC, x, ln, M, N, K, e, s);
+    return;
+  }
+  // prefill and batches: exact bf16 weights in the scratch, then the bf16 stage's own GEMM / batched GEMV
+  launch_dequant_mx4(Q, SC, w_scratch, N, K, s);
+  launch_linear(1, X, w_scratch, M, N, K, e, s);
+}
+
+// ------------------------------------------------------------------------------------
 // Greedy lm_head screening ("Head screening").  A greedy step needs one token id per row, not
 // 250 880 logits: an int8 shadow copy Qh of the tied embedding (quantize_rows_kernel's rule, made once at stage init)
 // is streamed instead of the bf16 rows -- half the bytes -- and yields for every vocabulary row n an approximate logit

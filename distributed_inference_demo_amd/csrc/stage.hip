@@ -59,6 +59,7 @@ enum { M_WEMB = 0, M_EMB_G = 1, M_EMB_B = 2, M_LNF_G = 3, M_LNF_B = 4, M_SCORE =
 struct Layer {
   void* t[T_NLAYER];
   float* sc[T_NLAYER];  // int8 stages: per-row scales of the four weight matrices (else null)
+  uint8_t* mxs[T_NLAYER];  // MXFP4 stages: E8M0 block scales of the four weight matrices (else null); t[] = codes
 };
 
 static bool is_matrix(int t) { return t == T_QKV_W || t == T_DENSE_W || t == T_FC1_W || t == T_FC2_W; }
@@ -107,9 +108,10 @@ struct bs_stage {
   bs_stage_desc d;
   int bf16 = 1;
   int q8 = 0;              // BS_FLAG_INT8_WEIGHTS: block matrices int8 + row scales
+  int mx4 = 0;             // BS_FLAG_MXFP4_WEIGHTS: block matrices E2M1 codes + E8M0 block scales
   int kv8 = 0;             // BS_FLAG_INT8_KV: int8 KV codes + fp32 scales, bf16 staging (kv_int8.hip)
   size_t esz = 2;
-  void* wtmp = nullptr;    // int8 stages: bf16 [4h][h] staging (init) and dequantized operand (prefill)
+  void* wtmp = nullptr;    // int8 / MXFP4 stages: bf16 [4h][h] staging (init) and dequantized operand (prefill)
   int hd = 0, L = 0;
   hipStream_t own = nullptr;
   // HBM
@@ -162,6 +164,7 @@ struct bs_stage {
   ProfClass prof;
   std::vector<std::pair<void*, size_t>> order;  // canonical weight order (BS_WEIGHTS_HOST layout)
   std::vector<std::pair<const float*, int>> order_q8;  // per order entry: (row scales, K) if int8, else (null, 0)
+  std::vector<std::pair<const uint8_t*, int>> order_mx;  // per order entry: (block scales, K) if MXFP4, else (null, 0)
   std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;  // captured decode steps
   float* logit_buf = nullptr;       // host-I/O logits staging
   size_t logit_cap = 0;
@@ -240,6 +243,13 @@ static int validate(const bs_stage_desc* d, bool from_file = false) {
   if (!d) return fail(BS_ERR_INVALID, "desc is NULL");
   if (d->hidden <= 0 || d->n_head <= 0 || d->hidden % d->n_head)
     return fail(BS_ERR_INVALID, "hidden must be a positive multiple of n_head");
+  if (d->flags & BS_FLAG_MXFP4_WEIGHTS) {  // before the general width check: its own status codes
+    if (d->flags & BS_FLAG_INT8_WEIGHTS)
+      return fail(BS_ERR_INVALID, "BS_FLAG_MXFP4_WEIGHTS and BS_FLAG_INT8_WEIGHTS exclude each other");
+    if (d->dtype != BS_DT_BFLOAT16) return fail(BS_ERR_UNSUPPORTED, "BS_FLAG_MXFP4_WEIGHTS needs dtype BFLOAT16");
+    if (d->hidden % 32)
+      return fail(BS_ERR_UNSUPPORTED, "BS_FLAG_MXFP4_WEIGHTS needs hidden to be a multiple of 32 (the MX block)");
+  }
   if (d->hidden % 32) return fail(BS_ERR_INVALID, "hidden must be a multiple of 32");
   const int hd = d->hidden / d->n_head;
   if (hd % 8 || hd > 128) return fail(BS_ERR_INVALID, "head_dim must be a multiple of 8 and <= 128");
@@ -254,7 +264,7 @@ static int validate(const bs_stage_desc* d, bool from_file = false) {
     return fail(BS_ERR_INVALID, "head vocab slice must be a 16-aligned sub-range of [0, vocab)");
   if (!from_file && d->weight_source != BS_WEIGHTS_SYNTHETIC && d->weight_source != BS_WEIGHTS_HOST)
     return fail(BS_ERR_INVALID, "unknown weight_source");
-  if (d->flags & ~(BS_FLAG_INT8_WEIGHTS | BS_FLAG_CLASSIFIER | BS_FLAG_INT8_KV))
+  if (d->flags & ~(BS_FLAG_INT8_WEIGHTS | BS_FLAG_CLASSIFIER | BS_FLAG_INT8_KV | BS_FLAG_MXFP4_WEIGHTS))
     return fail(BS_ERR_INVALID, "unknown desc flags");
   if ((d->flags & BS_FLAG_INT8_KV) && d->dtype != BS_DT_BFLOAT16)
     return fail(BS_ERR_INVALID, "BS_FLAG_INT8_KV needs dtype BFLOAT16");
@@ -449,6 +459,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   if (s->d.max_tokens <= 0) s->d.max_tokens = s->d.max_batch * 128;
   s->bf16 = desc->dtype == BS_DT_BFLOAT16;
   s->q8 = (desc->flags & BS_FLAG_INT8_WEIGHTS) != 0;
+  s->mx4 = (desc->flags & BS_FLAG_MXFP4_WEIGHTS) != 0;
   s->kv8 = (desc->flags & BS_FLAG_INT8_KV) != 0;
   s->esz = s->bf16 ? 2 : 4;
   s->n_labels = (desc->flags & BS_FLAG_CLASSIFIER) ? desc->n_labels : 0;
@@ -476,6 +487,9 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
       if (s->q8 && is_matrix(t)) {
         addb(lsz[t]);                                               // int8 [N][K]
         addb((t == T_FC1_W ? 4 * h : (t == T_QKV_W ? 3 * h : h)) * 4);  // fp32 scale [N]
+      } else if (s->mx4 && is_matrix(t)) {
+        addb(lsz[t] / 2);                                           // E2M1 codes, 16-B block records
+        addb(lsz[t] / 32);                                          // E8M0 scale [N][K / 32]
       } else {
         add(lsz[t]);
       }
@@ -499,6 +513,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
     for (int t = 0; t < T_NLAYER; t++) {
       s->layers[l].t[t] = s->wbase + offs[oi++];
       s->layers[l].sc[t] = (s->q8 && is_matrix(t)) ? (float*)(s->wbase + offs[oi++]) : nullptr;
+      s->layers[l].mxs[t] = (s->mx4 && is_matrix(t)) ? (uint8_t*)(s->wbase + offs[oi++]) : nullptr;
     }
   if (desc->is_last) { s->lnf_g = s->wbase + offs[oi++]; s->lnf_b = s->wbase + offs[oi++]; }
   if (s->n_labels) s->score = s->wbase + offs[oi++];
@@ -526,8 +541,23 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
             s->order_q8[i] = {s->layers[l].sc[t], (int)(t == T_FC2_W ? 4 * h : h)};
     if (hipMalloc(&s->wtmp, 4 * h * h * 2) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "int8 staging allocation failed"));
   }
-  // int8 matrices are produced in bf16 in the staging buffer, then quantized into the arena
+  s->order_mx.assign(s->order.size(), {nullptr, 0});
+  if (s->mx4) {
+    for (size_t i = 0; i < s->order.size(); i++)
+      for (int l = 0; l < s->L; l++)
+        for (int t = 0; t < T_NLAYER; t++)
+          if (s->layers[l].mxs[t] && s->order[i].first == s->layers[l].t[t])
+            s->order_mx[i] = {s->layers[l].mxs[t], (int)(t == T_FC2_W ? 4 * h : h)};
+    if (hipMalloc(&s->wtmp, 4 * h * h * 2) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "MXFP4 staging allocation failed"));
+  }
+  // int8 / MXFP4 matrices are produced in bf16 in the staging buffer, then quantized into the arena
+  auto staged = [&](size_t i) { return s->order_q8[i].first != nullptr || s->order_mx[i].first != nullptr; };
   auto quantize = [&](size_t i) {
+    if (s->order_mx[i].first) {
+      const int K = s->order_mx[i].second, N = (int)(s->order[i].second / K);
+      launch_quantize_mx4(s->wtmp, (uint8_t*)s->order[i].first, (uint8_t*)s->order_mx[i].first, N, K, s->own);
+      return;
+    }
     const int K = s->order_q8[i].second, N = (int)(s->order[i].second / K);
     launch_quantize_rows(s->wtmp, (int8_t*)s->order[i].first, (float*)s->order_q8[i].first, N, K, s->own);
   };
@@ -546,7 +576,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
     std::string why;
     for (size_t oi2 = 0; oi2 < s->order.size(); oi2++) {
       const auto& o = s->order[oi2];
-      const bool q = s->order_q8[oi2].first != nullptr;
+      const bool q = staged(oi2);
       char* dst = (char*)(q ? s->wtmp : o.first);
       const st::Tensor* t = find_entry(*ck, fes[oi2], &why);
       if (!t || fes[oi2].first + o.second > t->numel()) {
@@ -598,7 +628,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
     if (s->emb_b) launch_gen_fill(s->emb_b, s->bf16, h, tensor_key(seed, -1, M_EMB_B), 3, s->own);
     for (int l = 0; l < s->L; l++)
       for (int t = 0; t < T_NLAYER; t++) {
-        const bool q = s->layers[l].sc[t] != nullptr;
+        const bool q = s->layers[l].sc[t] != nullptr || s->layers[l].mxs[t] != nullptr;
         launch_gen_fill(q ? s->wtmp : s->layers[l].t[t], s->bf16, lsz[t], tensor_key(seed, desc->layer_begin + l, t),
                         layer_kind(t), s->own);
         if (q) {
@@ -622,7 +652,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
     const float* src = desc->host_weights;
     for (size_t oi2 = 0; oi2 < s->order.size(); oi2++) {
       const auto& o = s->order[oi2];
-      const bool q = s->order_q8[oi2].first != nullptr;
+      const bool q = staged(oi2);
       for (size_t i = 0; i < o.second; i += chunk) {
         const size_t n = std::min(chunk, o.second - i);
         if (hipMemcpyAsync(bounce, src + i, n * sizeof(float), hipMemcpyHostToDevice, s->own) != hipSuccess) {
@@ -760,6 +790,7 @@ extern "C" int bs_read_weights(const bs_stage* s, uint64_t offset, uint64_t coun
   std::vector<uint16_t> tmp;
   std::vector<int8_t> qtmp;
   std::vector<float> stmp;
+  std::vector<uint8_t> ctmp, etmp;
   for (size_t oi = 0; oi < s->order.size(); oi++) {
     const auto& o = s->order[oi];
     const uint64_t b = base, e = base + o.second;
@@ -769,7 +800,30 @@ extern "C" int bs_read_weights(const bs_stage* s, uint64_t offset, uint64_t coun
     const uint64_t n = hi - lo;
     const char* src = (const char*)o.first + (lo - b) * s->esz;
     float* dst = out + (lo - offset);
-    if (s->order_q8[oi].first) {  // int8 matrix: dequantized values Q * scale
+    if (s->order_mx[oi].first) {  // MXFP4 matrix: +-grid[code] * 2^(E - 127), codes in rotated block records
+      const int K = s->order_mx[oi].second, nb = K / 32;
+      const uint64_t b0 = (lo - b) / 32, b1 = (hi - b - 1) / 32;  // blocks of the matrix, row-major
+      ctmp.resize((b1 - b0 + 1) * 16);
+      etmp.resize(b1 - b0 + 1);
+      HIP_TRY(hipMemcpy(ctmp.data(), (const uint8_t*)o.first + b0 * 16, ctmp.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(etmp.data(), s->order_mx[oi].first + b0, etmp.size(), hipMemcpyDeviceToHost));
+      static const float grid[16] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f, -0.f, -0.5f, -1.f, -1.5f, -2.f, -3.f, -4.f, -6.f};
+      for (uint64_t blk = b0; blk <= b1; blk++) {
+        const float X = std::ldexp(1.0f, (int)etmp[blk - b0] - 127);
+        const uint8_t* rec = &ctmp[(blk - b0) * 16];
+        const int rot = (int)((blk % nb) >> 2);
+        float v[32];
+        for (int g = 0; g < 4; g++) {
+          const uint8_t* dw = rec + 4 * ((g - rot) & 3);
+          for (int j = 0; j < 4; j++) {
+            v[8 * g + 2 * j] = grid[dw[j] & 15] * X;
+            v[8 * g + 2 * j + 1] = grid[dw[j] >> 4] * X;
+          }
+        }
+        const uint64_t k0 = std::max<uint64_t>(blk * 32, lo - b), k1 = std::min<uint64_t>(blk * 32 + 32, hi - b);
+        for (uint64_t k = k0; k < k1; k++) dst[k - (lo - b)] = v[k - blk * 32];
+      }
+    } else if (s->order_q8[oi].first) {  // int8 matrix: dequantized values Q * scale
       const int K = s->order_q8[oi].second;
       const uint64_t r0 = (lo - b) / K, r1 = (hi - b - 1) / K;
       qtmp.resize(n);
@@ -1118,10 +1172,21 @@ static double gemv_bytes_q8(const bs_stage* s, int M, int N, int K, int out_byte
   return (double)N * K + (double)N * 4 + (double)N * s->esz + (double)M * K * s->esz + (double)M * N * out_bytes;
 }
 
-// Block matrix t of a layer: int8 stages stream the int8 weights (launch_linear_q8).
+// Algorithmic bytes of one MXFP4 weight GEMV launch: codes and block scales (0.53125 B per weight) + bias +
+// activations.
+static double gemv_bytes_mx4(const bs_stage* s, int M, int N, int K, int out_bytes) {
+  return (double)N * K * 0.53125 + (double)N * s->esz + (double)M * K * s->esz + (double)M * N * out_bytes;
+}
+
+// Block matrix t of a layer: int8 stages stream the int8 weights (launch_linear_q8), MXFP4 stages the fp4 codes
+// (launch_linear_mx4).
 static void wlinear(bs_stage* s, hipStream_t st, const void* X, const Layer& w, int t, int M, int N, int K,
                     const Epi& ep, int out_bytes) {
-  if (!w.sc[t]) {
+  if (w.mxs[t]) {
+    const bool gemv = linear_mx4_gemv(M, N, K);
+    ProfScope p(s, st, gemv ? 1 : 2, gemv ? gemv_bytes_mx4(s, M, N, K, out_bytes) : 2.0 * M * N * K);
+    launch_linear_mx4(X, (const uint8_t*)w.t[t], w.mxs[t], s->wtmp, M, N, K, ep, st);
+  } else if (!w.sc[t]) {
     linear(s, st, X, w.t[t], M, N, K, ep, out_bytes);
   } else if (M <= 32) {  // int8 GEMV / batched tile GEMV: weight-stream bound
     ProfScope p(s, st, 1, gemv_bytes_q8(s, M, N, K, out_bytes));
@@ -1134,6 +1199,16 @@ static void wlinear(bs_stage* s, hipStream_t st, const void* X, const Layer& w, 
 
 static void wlinear_ln(bs_stage* s, hipStream_t st, const float* x, const void* g, const void* b, const Layer& w,
                        int t, int M, int N, int K, const Epi& ep, int out_bytes) {
+  if (w.mxs[t]) {
+    if (linear_mx4_ln_fused(M, K)) {
+      ProfScope p(s, st, 1, gemv_bytes_mx4(s, M, N, K, out_bytes));
+      launch_linear_mx4_ln(x, 1, 0, g, b, s->d.ln_eps, (const uint8_t*)w.t[t], w.mxs[t], M, N, K, ep, st);
+      return;
+    }
+    launch_ln_rows(x, 1, 0, g, b, s->d.ln_eps, s->xn, M, K, st);
+    wlinear(s, st, s->xn, w, t, M, N, K, ep, out_bytes);
+    return;
+  }
   if (!w.sc[t]) {
     linear_ln(s, st, x, 1, 0, g, b, w.t[t], M, N, K, ep, out_bytes);
     return;
@@ -1187,7 +1262,7 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
   const float* cur = nullptr;
   const int* ids = nullptr;
   // bf16 decode of <= 2 rows: the embedding gather and its LayerNorm run in layer 0's LN + QKV kernel
-  const bool emb_fused = d.is_first && s->bf16 && !s->q8 && M <= 2 && s->L > 0;
+  const bool emb_fused = d.is_first && s->bf16 && !s->q8 && !s->mx4 && M <= 2 && s->L > 0;
   if (d.is_first) {
     ids = (const int*)in;
     if (host_io) {
@@ -1246,8 +1321,9 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     // a split decode context merges in the dense GEMV's prologue when that kernel can take it
     const int nsplit = S == 1 ? attention_decode_splits(B, nh, s->max_chunks) : 1;
     a.defer_merge = s->bf16 && nsplit > 1 &&
-                    (w.sc[T_DENSE_W] ? linear_q8_parts_supported(M, h, hd, nsplit)
-                                     : linear_parts_supported(M, h, hd, nsplit));
+                    (w.mxs[T_DENSE_W] ? linear_mx4_parts_supported(M, h, hd, nsplit)
+                     : w.sc[T_DENSE_W] ? linear_q8_parts_supported(M, h, hd, nsplit)
+                                       : linear_parts_supported(M, h, hd, nsplit));
     // a = x + dense(ctx)
     Epi e2{};
     e2.kind = EPI_RESID; e2.bias = w.t[T_DENSE_B]; e2.out_f32 = s->attn; e2.resid = cur; e2.ldo = h;
@@ -1267,8 +1343,11 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     }
     if (a.defer_merge) {
       const AttnParts parts{s->part_acc, s->part_ml, nsplit, nh, hd, s->max_chunks, slot};
-      ProfScope p(s, st, 1, w.sc[T_DENSE_W] ? gemv_bytes_q8(s, M, h, h, 4) : gemv_bytes(s, M, h, h, 4));
-      if (w.sc[T_DENSE_W]) launch_linear_q8_parts(parts, (const int8_t*)w.t[T_DENSE_W], w.sc[T_DENSE_W], M, h, h, e2, st);
+      ProfScope p(s, st, 1, w.mxs[T_DENSE_W] ? gemv_bytes_mx4(s, M, h, h, 4)
+                            : w.sc[T_DENSE_W] ? gemv_bytes_q8(s, M, h, h, 4) : gemv_bytes(s, M, h, h, 4));
+      if (w.mxs[T_DENSE_W])
+        launch_linear_mx4_parts(parts, (const uint8_t*)w.t[T_DENSE_W], w.mxs[T_DENSE_W], M, h, h, e2, st);
+      else if (w.sc[T_DENSE_W]) launch_linear_q8_parts(parts, (const int8_t*)w.t[T_DENSE_W], w.sc[T_DENSE_W], M, h, h, e2, st);
       else launch_linear_parts(parts, w.t[T_DENSE_W], M, h, h, e2, st);
     } else {
       wlinear(s, st, s->ctx, w, T_DENSE_W, M, h, h, with_splitk(s, e2), 4);

@@ -519,6 +519,8 @@ def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb
                          "leave a slice without a 16-column tile")
     if model.int8_weights and dtype != "bf16":
         raise ValueError(f"{model.name}: weight-only int8 stages need dtype bf16 (got {dtype})")
+    if model.mxfp4_weights and dtype != "bf16":
+        raise ValueError(f"{model.name}: weight-only MXFP4 stages need dtype bf16 (got {dtype})")
     if kv_int8 and dtype != "bf16":
         raise ValueError(f"an int8 KV cache needs dtype bf16 (got {dtype})")
     if kv_int8 and executor_factory is not None:
@@ -534,7 +536,7 @@ def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb
                    device=device.index if device.type == "cuda" else 0, max_batch=mb_rows * n_mb,
                    max_ctx=max_ctx, max_tokens=mb_rows * max_seq, seed=seed, is_first=is_first,
                    is_last=is_last and not head_split, head_slice=hslice, int8_weights=model.int8_weights,
-                   n_labels=n_labels if is_last else 0, kv_int8=kv_int8)
+                   n_labels=n_labels if is_last else 0, kv_int8=kv_int8, mxfp4_weights=model.mxfp4_weights)
         ex = StageExecutor(st)
     else:
         kw = {"n_labels": n_labels} if (n_labels and is_last) else {}

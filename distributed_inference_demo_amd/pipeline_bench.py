@@ -65,6 +65,8 @@ def stage_step_bytes(model, lb, le, rows, ctx, first, last, hslice, w_bytes, kv_
         b += (hslice[1] - hslice[0]) * model.hidden * w_bytes + 2 * model.hidden * w_bytes
     if model.int8_weights:  # block matrices: 1 byte per weight + one fp32 scale per output row
         b -= (le - lb) * (12.0 * model.hidden * model.hidden * 1 - 9.0 * model.hidden * 4)
+    if model.mxfp4_weights:  # block matrices: 4-bit codes + one scale byte per 32 weights
+        b -= (le - lb) * 12.0 * model.hidden * model.hidden * (w_bytes - config.MXFP4_BYTES_PER_WEIGHT)
     return b
 
 
@@ -246,6 +248,8 @@ def bench_pipeline(args, backend="nccl", executor_factory=None):
     model = config.get(args.model)
     if getattr(args, "weights", "bf16") == "int8":
         model = config.get(model.name if model.int8_weights else model.name + "-int8")
+    elif getattr(args, "weights", "bf16") == "mxfp4":
+        model = config.get(model.name if model.mxfp4_weights else model.name + "-mxfp4")
     prof_rounds = 0 if getattr(args, "no_profile", False) else 8
     head_split = not getattr(args, "no_head_split", False)
     dtype, seed = args.dtype, args.seed

@@ -42,6 +42,7 @@ BS_STEP_LOGITS = 2
 BS_FLAG_INT8_WEIGHTS = 1  # bs_stage_desc.flags: weight-only int8 block matrices
 BS_FLAG_CLASSIFIER = 2    # bs_stage_desc.flags: sequence-classification tail (score head, class ids out)
 BS_FLAG_INT8_KV = 4       # bs_stage_desc.flags: int8 KV cache, one fp32 scale per (position, head) vector
+BS_FLAG_MXFP4_WEIGHTS = 8  # bs_stage_desc.flags: weight-only MXFP4 block matrices (E2M1 codes + E8M0 block scales)
 
 DTYPES = {
     1: np.float32, 2: np.uint8, 3: np.int8, 4: np.uint16, 5: np.int16, 6: np.int32, 7: np.int64,
@@ -183,13 +184,16 @@ class Stage:
     def __init__(self, hidden, n_head, n_layer, vocab, layer_begin, layer_end, *, dtype="bf16", device=0,
                  max_batch=1, max_ctx=2048, max_tokens=0, seed=0, eps=1e-5, host_weights=None,
                  is_first=None, is_last=None, head_slice=None, int8_weights=False, weights_file=None, n_labels=0,
-                 kv_int8=False):
+                 kv_int8=False, mxfp4_weights=False):
         """weights_file: a safetensors checkpoint (or its sharded *.index.json) of HF BLOOM tensors;
         the stage maps it and loads only its own layer range (bs_init_stage_file).
         n_labels > 0: a sequence-classification tail (BS_FLAG_CLASSIFIER, last stage): forwards return class ids
         and logits [batch][n_labels] instead of tokens and vocabulary logits.
         kv_int8: the KV cache holds int8 codes + one fp32 scale per (position, head) vector (BS_FLAG_INT8_KV, bf16
-        stages); read_kv returns the dequantised values."""
+        stages); read_kv returns the dequantised values.
+        mxfp4_weights: the four block matrices are held as OCP MXFP4 (BS_FLAG_MXFP4_WEIGHTS, bf16 stages, opt-in:
+        round-to-nearest 4-bit weights are lossy); read_weights returns the dequantised values, which are exact in
+        bf16, so a plain bf16 stage given them as host_weights is the same model."""
         if weights_file is not None and host_weights is not None:
             raise ValueError("pass host_weights or weights_file, not both")
         d = StageDesc()
@@ -201,6 +205,8 @@ class Stage:
         d.device, d.max_batch, d.max_ctx, d.max_tokens = device, max_batch, max_ctx, max_tokens
         d.seed = seed
         d.flags = BS_FLAG_INT8_WEIGHTS if int8_weights else 0  # bloom*-int8 variants (server.py:796-799)
+        if mxfp4_weights:
+            d.flags |= BS_FLAG_MXFP4_WEIGHTS
         if kv_int8:
             d.flags |= BS_FLAG_INT8_KV
         if n_labels:

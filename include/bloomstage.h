@@ -97,6 +97,21 @@ typedef enum {
  *   bs_read_kv returns the dequantised fp32 values; bs_stage_info reports
  *   kv_bytes = layers * 2 * max_batch * n_head * max_ctx * (head_dim + 4). */
 #define BS_FLAG_INT8_KV 4
+/* desc->flags.  BS_FLAG_MXFP4_WEIGHTS (bf16 stages; BS_ERR_UNSUPPORTED on an fp32 stage or when hidden is not a
+ * multiple of 32; BS_ERR_INVALID together with BS_FLAG_INT8_WEIGHTS): weight-only OCP MXFP4 for the four block
+ * matrices (qkv, dense, fc1, fc2): 4-bit E2M1 codes with one E8M0 scale byte per block of 32 weights, 0.53125 bytes
+ * per weight.  Orthogonal to BS_FLAG_CLASSIFIER and BS_FLAG_INT8_KV.  Embeddings, LayerNorms, biases, the tied
+ * lm_head (with its int8 screening copy) and the classifier score matrix stay bf16; activations stay bf16/fp32.
+ *   Rule (OCP Microscaling Formats v1.0, round to nearest without calibration), per block = 32 consecutive k of one
+ *   output row of the bf16 weight W: amax = max|W| over the block.  amax < 2^-100: E = 127 and every code is 0.
+ *   Otherwise E = (biased fp32 exponent field of amax) - 2, i.e. floor(log2 amax) - emax with emax = 2 for E2M1.
+ *   X = 2^(E - 127); |W| / X (exact) is rounded to the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even
+ *   code, anything above 6 saturates to 6.  A code is the 3-bit grid index plus a sign bit (bit 3); the sign of a
+ *   zero code is unspecified.  The dequantised value +-grid[index] * X is exact in bf16, so the stage computes the
+ *   bf16 model whose host weights are the dequantised values.
+ *   bs_read_weights returns the dequantised values; bs_stage_info reports the real storage under weight_bytes.  The
+ *   device layout is private to the library. */
+#define BS_FLAG_MXFP4_WEIGHTS 8
 
 typedef struct bs_stage_desc {
   /* model (HF BloomConfig fields) */
@@ -194,7 +209,7 @@ int bs_forward(bs_stage *stage, const bs_step *step, const void *in, void *out, 
  *       both).
  * Results are bit-identical from run to run (no floating-point atomics, partials folded in a fixed order).
  * BS_ERR_STATE on a classifier stage or a stage without ln_f and the whole lm_head (not last); BS_ERR_UNSUPPORTED on
- * an fp32 stage; BS_FLAG_INT8_WEIGHTS / BS_FLAG_INT8_KV stages score (the head stays bf16).  batch * seq <=
+ * an fp32 stage; BS_FLAG_INT8_WEIGHTS / BS_FLAG_MXFP4_WEIGHTS / BS_FLAG_INT8_KV stages score (the head stays bf16).  batch * seq <=
  * max_tokens.  The first scoring call allocates the head's per-split partials and the host-I/O staging (well under
  * max_tokens * vocab bytes; no buffer grows with batch * seq * vocab), counted under workspace_bytes from then on. */
 int bs_forward_score(bs_stage *stage, const bs_step *step, const void *in, const int32_t *targets,
