@@ -108,6 +108,17 @@ size_t attention_workspace_floats(int B, int n_head, int head_dim, int max_ctx, 
 // Context splits per (row, head) of a decode attention launch (1 = the block writes ctx itself).
 int attention_decode_splits(int B, int n_head, int max_chunks);
 
+// ---- Verify pass (BS_STEP_VERIFY; attn_verify.hip) ----
+// Attention of 2 <= a.S <= 8 queries per row, a.B * a.S <= kVerifyMaxTokens, head_dim <= 128, over the warm cache:
+// grid (n_head, B, nsplit) with nsplit = attention_decode_splits(B, n_head, chunks of max_ctx), every row's length
+// from a.past_dev -- nothing per call on the host side, so the launch can be captured.  a.part_acc / a.part_ml are
+// the verify partials ([B * S][n_head][stride][head_dim] and [..][2], sized for kVerifyMaxTokens positions) and
+// a.max_chunks their split stride (attention_verify_split_stride); a.tickets as for the decode kernel.  Split
+// partials are folded in index order by the last block of each (row, head); bit-identical from run to run.
+constexpr int kVerifyMaxTokens = 32;
+int attention_verify_split_stride(int n_head, int max_chunks);
+void launch_attention_verify(int is_bf16, const AttnArgs& a, hipStream_t s);
+
 // ---- Int8 KV cache (bf16 stages with BS_FLAG_INT8_KV; kv_int8.hip) ----
 // The fp32 scales beside the int8 codes of one layer ([max_batch][heads][max_ctx], K and V), and the bf16 staging
 // buffers the QKV epilogue writes a call's new K / V rows to ([B][heads][lmax][hd], slot 0).
@@ -143,9 +154,10 @@ void launch_linear_parts(const AttnParts& p, const void* W, int M, int N, int K,
 // Reduce the per-tile keys of each row (and keys_in[m] if given) -> keys_out[m] / tokens[m] (either optional).
 // past_adv (optional): past_adv[m] += seq for every row (the decode step's last kernel advances the
 // device copy of the cached lengths; stage.hip skips set_past when the host's next step matches it).
+// adv_rows >= 0: only rows m < adv_rows advance (a verify pass reduces B * S positions of B rows).
 void launch_argmax_finalize(const unsigned long long* keys, int M, int ntiles, const unsigned long long* keys_in,
                             unsigned long long* keys_out, int* tokens, hipStream_t s, int* past_adv = nullptr,
-                            int seq = 0);
+                            int seq = 0, int adv_rows = -1);
 // ---- Greedy lm_head screening (bf16 stages, M <= 2, K <= 4096; kernels.hip "Greedy lm_head screening") ----
 // The int8 shadow copy of the tied embedding with its per-row bound constants (made once at stage init) and the
 // per-step buffers of the screened tail; ntiles = V / 16.

@@ -2952,7 +2952,7 @@ void launch_attention(int is_bf16, const AttnArgs& a, hipStream_t s) {
 __global__ __launch_bounds__(1024) void argmax_finalize_kernel(const unsigned long long* keys, int ntiles,
                                                                 const unsigned long long* keys_in,
                                                                 unsigned long long* keys_out, int* tokens,
-                                                                int* past_adv, int seq) {
+                                                                int* past_adv, int seq, int adv_rows) {
   __shared__ unsigned long long sh[16];
   const int m = blockIdx.x;
   const unsigned long long* kr = keys + (size_t)m * ntiles;
@@ -2980,14 +2980,16 @@ __global__ __launch_bounds__(1024) void argmax_finalize_kernel(const unsigned lo
       if (keys_in) best = keys_in[m] > best ? keys_in[m] : best;
       if (keys_out) keys_out[m] = best;
       if (tokens) tokens[m] = (int)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
-      if (past_adv) past_adv[m] += seq;
+      if (past_adv && m < adv_rows) past_adv[m] += seq;
     }
   }
 }
 
 void launch_argmax_finalize(const unsigned long long* keys, int M, int ntiles, const unsigned long long* keys_in,
-                            unsigned long long* keys_out, int* tokens, hipStream_t s, int* past_adv, int seq) {
-  argmax_finalize_kernel<<<M, 1024, 0, s>>>(keys, ntiles, keys_in, keys_out, tokens, past_adv, seq);
+                            unsigned long long* keys_out, int* tokens, hipStream_t s, int* past_adv, int seq,
+                            int adv_rows) {
+  argmax_finalize_kernel<<<M, 1024, 0, s>>>(keys, ntiles, keys_in, keys_out, tokens, past_adv, seq,
+                                            adv_rows < 0 ? M : adv_rows);
 }
 
 // ------------------------------------------------------------------------------------

@@ -65,13 +65,13 @@ struct Layer {
 static bool is_matrix(int t) { return t == T_QKV_W || t == T_DENSE_W || t == T_FC1_W || t == T_FC2_W; }
 
 struct GraphKey {
-  int B, slot, flags;
+  int B, seq, slot, flags;
   const void* in;
   void* out;
   float* logits;
   hipStream_t st;
   bool operator==(const GraphKey& o) const {
-    return B == o.B && slot == o.slot && flags == o.flags && in == o.in && out == o.out && logits == o.logits &&
+    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && in == o.in && out == o.out && logits == o.logits &&
            st == o.st;
   }
 };
@@ -193,6 +193,15 @@ struct bs_stage {
   int* sc_targets = nullptr;  // [max_tokens]
   int* sc_top = nullptr;      // [max_tokens]
   float* sc_scores = nullptr; // [max_tokens][3]
+  // BS_STEP_VERIFY (attn_verify.hip): the short-query attention's split partials for kVerifyMaxTokens positions, the
+  // tail's argmax keys and ids of every position, one allocation made by the first verify call (null: never verified)
+  char* vf_base = nullptr;
+  size_t vf_bytes = 0;
+  float* vf_acc = nullptr;             // [kVerifyMaxTokens][n_head][vf_stride][hd]
+  float* vf_ml = nullptr;              // [kVerifyMaxTokens][n_head][vf_stride][2]
+  int vf_stride = 0;                   // attention_verify_split_stride
+  unsigned long long* vf_keys = nullptr;  // [kVerifyMaxTokens][V/16] (last stage)
+  int* vf_tok = nullptr;               // [kVerifyMaxTokens] host-I/O staging of the ids
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -332,6 +341,7 @@ static void free_stage(bs_stage* s) {
   if (s->wtmp) hipFree(s->wtmp);
   if (s->hs_base) hipFree(s->hs_base);
   if (s->sc_base) hipFree(s->sc_base);
+  if (s->vf_base) hipFree(s->vf_base);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
@@ -777,8 +787,8 @@ extern "C" int bs_stage_info(const bs_stage* s, bs_stage_desc* d, uint64_t* wb, 
   if (d) *d = s->d;
   if (wb) *wb = s->wbytes;
   if (kvb) *kvb = s->kvbytes;
-  // the head-screening shadow copy, the int8 KV staging and the scoring buffers count as workspace
-  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
+  // the head-screening shadow copy, the int8 KV staging, the scoring and the verify buffers count as workspace
+  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + s->vf_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
   return BS_OK;
 }
 
@@ -1256,6 +1266,7 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
   const int M = B * S;
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
+  const bool verify = (step->flags & BS_STEP_VERIFY) != 0;  // forward_impl checked the shape and the stage
   const int h = d.hidden, V = d.vocab, hd = s->hd, nh = d.n_head;
 
   // ---- input
@@ -1327,7 +1338,13 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     // a = x + dense(ctx)
     Epi e2{};
     e2.kind = EPI_RESID; e2.bias = w.t[T_DENSE_B]; e2.out_f32 = s->attn; e2.resid = cur; e2.ldo = h;
-    if (!s->kv8) {
+    if (verify) {
+      // short-query split-context attention on a static grid (attn_verify.hip): every row's length from past_dev
+      ProfScope p(s, st, 3, ctx_sum * nh * hd * 2 * s->esz);
+      AttnArgs av = a;
+      av.part_acc = s->vf_acc; av.part_ml = s->vf_ml; av.max_chunks = s->vf_stride;
+      launch_attention_verify(s->bf16, av, st);
+    } else if (!s->kv8) {
       ProfScope p(s, st, 3, ctx_sum * nh * hd * 2 * s->esz);
       launch_attention(s->bf16, a, st);
     } else if (S == 1) {
@@ -1399,6 +1416,25 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     if (host_io) {
       if (top) HIP_TRY(hipMemcpyAsync(sc->top_ids, top, (size_t)M * 4, hipMemcpyDeviceToHost, st));
       if (scr) HIP_TRY(hipMemcpyAsync(sc->scores, scr, (size_t)M * 12, hipMemcpyDeviceToHost, st));
+    }
+  } else if (d.is_last && verify) {
+    // verify tail: ln_f of all M positions, the tied lm_head with the argmax epilogue over M rows (never screened),
+    // the first index of the largest logit at every position; the finalize is the pass's last kernel and advances
+    // past_dev by S for the B rows
+    Epi e{};
+    e.kind = EPI_ARGMAX; e.keys = s->vf_keys; e.logits = want_logits && !host_io ? logits : nullptr; e.ldo = V;
+    float* dev_logits = nullptr;
+    if (want_logits && host_io) {
+      int rc = logits_staging(s, (size_t)M * V * 4, st, &dev_logits);
+      if (rc != BS_OK) return rc;
+      e.logits = dev_logits;
+    }
+    int* tok_out = host_io ? s->vf_tok : (int*)out;
+    linear_ln(s, st, cur, 1, 0, s->lnf_g, s->lnf_b, s->wemb, M, V, h, with_splitk(s, e), 0);
+    launch_argmax_finalize(s->vf_keys, M, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S, B);
+    if (host_io) {
+      HIP_TRY(hipMemcpyAsync(out, s->vf_tok, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+      if (dev_logits) HIP_TRY(hipMemcpyAsync(logits, dev_logits, (size_t)M * V * 4, hipMemcpyDeviceToHost, st));
     }
   } else if (d.is_last) {
     // ln_f on each row's last position, tied lm_head, token pick (greedy argmax or top-k sample)
@@ -1557,6 +1593,18 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
                                           " positions exceed the staging capacity of " +
                                           std::to_string(s->kv_stage_cap) + " (max(max_tokens, max_ctx))");
   }
+  const bool verify = (step->flags & BS_STEP_VERIFY) != 0;
+  if (verify) {
+    if (sc) return fail(BS_ERR_INVALID, "BS_STEP_VERIFY is not valid for a scoring pass");
+    if (S < 2 || S > 8 || M > kVerifyMaxTokens)
+      return fail(BS_ERR_INVALID, "a verify pass needs 2 <= seq <= 8 and batch * seq <= 32");
+    if (s->kv8) return fail(BS_ERR_UNSUPPORTED, "BS_STEP_VERIFY on an int8 KV cache is not supported");
+    if (s->hd > 128) return fail(BS_ERR_UNSUPPORTED, "BS_STEP_VERIFY needs head_dim <= 128");
+    if (s->n_labels) return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a classifier stage");
+    if (s->top_k > 1) return fail(BS_ERR_STATE, "BS_STEP_VERIFY needs the greedy pick (bs_set_sampling top_k <= 1)");
+    if (d.is_last && (!s->wemb || s->hv0 != 0 || s->hv1 != d.vocab))
+      return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a last stage needs the whole lm_head");
+  }
   if (!in || (!out && !sc)) return fail(BS_ERR_INVALID, "in/out is NULL");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   if (want_logits && (!d.is_last || !logits)) return fail(BS_ERR_INVALID, "logits requested on a non-last stage or NULL");
@@ -1569,8 +1617,26 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   BS_TRACE("B=%d S=%d slot=%d flags=%u stream=%p hipSetDevice", B, S, slot, (unsigned)step->flags, stream);
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  if (verify && !s->vf_base) {  // first verify call: split partials of the attention, keys and ids of every position
+    s->vf_stride = attention_verify_split_stride(d.n_head, s->max_chunks);
+    const size_t accf = (size_t)kVerifyMaxTokens * d.n_head * s->vf_stride * s->hd;
+    const size_t mlf = (size_t)kVerifyMaxTokens * d.n_head * s->vf_stride * 2;
+    const size_t sizes[4] = {accf * 4, mlf * 4, d.is_last ? (size_t)kVerifyMaxTokens * (d.vocab / 16) * 8 : 0,
+                             (size_t)kVerifyMaxTokens * 4};
+    size_t vo[4], off = 0;
+    for (int i = 0; i < 4; i++) { vo[i] = off; off = align_up(off + sizes[i], 256); }
+    if (hipMalloc((void**)&s->vf_base, off) != hipSuccess) {
+      s->vf_base = nullptr;
+      return fail(BS_ERR_OOM, "verify buffers allocation failed (" + std::to_string(off) + " B)");
+    }
+    s->vf_bytes = off;
+    s->vf_acc = (float*)(s->vf_base + vo[0]);
+    s->vf_ml = (float*)(s->vf_base + vo[1]);
+    s->vf_keys = (unsigned long long*)(s->vf_base + vo[2]);
+    s->vf_tok = (int*)(s->vf_base + vo[3]);
+  }
 
-  // Decode steps on device buffers replay a captured hipGraph: the kernels read past_len from
+  // Decode steps and verify passes on device buffers replay a captured hipGraph: the kernels read past_len from
   // device memory, set by one small kernel ahead of the replay -- unless the last forward (a last
   // stage's, whose token pick advances past_dev by its seq) already left exactly these values there,
   // on this same stream: a forward on another stream is not ordered behind that advance, so it always
@@ -1578,9 +1644,9 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   const bool past_matches = s->past_next_valid && s->past_stream == st && (int)s->past_next.size() == B &&
                             std::equal(pasts.begin(), pasts.end(), s->past_next.begin());
   s->past_next_valid = false;  // until this forward is enqueued
-  const bool graph = S == 1 && !host_io && s->prof.cls == 0 && s->graphs_on && !sc;  // scoring is always eager
+  const bool graph = (S == 1 || verify) && !host_io && s->prof.cls == 0 && s->graphs_on && !sc;  // scoring is always eager
   if (graph) {
-    GraphKey key{B, slot, step->flags, in, out, logits, st};
+    GraphKey key{B, S, slot, step->flags, in, out, logits, st};
     hipGraphExec_t exec = nullptr;
     for (auto& g : s->graphs)
       if (g.first == key) { exec = g.second; break; }
@@ -1600,6 +1666,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
       hipGraphDestroy(gr);
       if (ie != hipSuccess) return fail(BS_ERR_DEVICE, std::string("graph instantiate: ") + hipGetErrorString(ie));
       if (s->graphs.size() >= 64) {
+        HIP_TRY(hipStreamSynchronize(st));  // the evicted graph may still be replaying on this stream
         hipGraphExecDestroy(s->graphs.front().second);
         s->graphs.erase(s->graphs.begin());
       }
@@ -1623,7 +1690,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   BS_TRACE("hipGetLastError");
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
-  s->hs_last_rows = !sc && head_screened(s, B, want_logits) ? B : 0;
+  s->hs_last_rows = !sc && !verify && head_screened(s, B, want_logits) ? B : 0;
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)
     s->past_next.assign(pasts.begin(), pasts.end());
     for (int& p : s->past_next) p += S;

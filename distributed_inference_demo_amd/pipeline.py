@@ -66,6 +66,17 @@ class StageExecutor:
         self._run(lambda h: self.stage.forward(inp, out, batch, seq, slot=slot, past_len=past_len, stream=h),
                   (inp, out))
 
+    def verify(self, inp, out, batch, seq, slot, past_len, logits=None):
+        """A BS_STEP_VERIFY pass (Stage.forward(verify=True)): greedy ids of every position on the last stage,
+        ordered like forward."""
+        sh = self._sh if self._sh is not None else torch.cuda.current_stream().cuda_stream
+        if sh:
+            self.stage.forward(inp, out, batch, seq, slot=slot, past_len=past_len, logits=logits, stream=sh,
+                               verify=True)
+            return
+        self._run(lambda h: self.stage.forward(inp, out, batch, seq, slot=slot, past_len=past_len, logits=logits,
+                                               stream=h, verify=True), (inp, out, logits))
+
     def score(self, inp, targets, top_ids, scores, batch, seq, slot, past_len):
         """Teacher-forced scoring pass of the last stage (Stage.score), ordered like forward."""
         sh = torch.cuda.current_stream().cuda_stream

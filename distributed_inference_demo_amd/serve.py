@@ -30,6 +30,12 @@ together, `core_pool_size` rows a pass, and rank 0 returns each sample's class i
 --score is the scoring task (no counterpart in the reference): every sample's prompt is one teacher-forced pass
 (pipeline.score, bs_forward_score on the last stage), `core_pool_size` samples a pass, and rank 0 returns each
 sample's summed log-likelihood, token count and perplexity.
+--speculate K is speculative decoding on one GPU (speculative.py; no counterpart in the reference): the samples are
+decoded one after another in KV row 0, a drafter (--draft ngram: prompt lookup; --draft MODEL: a draft model with the
+same vocabulary, e.g. the target's "-int8" variant) proposes up to K tokens a round and one BS_STEP_VERIFY pass of
+the target emits the agreeing prefix plus one token.  The tokens are plain greedy decoding's; rank 0 also returns
+the acceptance statistics.  One stage only: the ranks of a pipeline derive their schedule from the prompt lengths
+alone, and how many tokens a pass accepts depends on the data.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax instead of unseeded top-k, token ids in (no tokenizer).
 
@@ -68,10 +74,21 @@ class RunConfig:
     prefill: bool = True          # an admitted sample's prompt as one prefill pass of its row (else a token a round)
     kv: str = "bf16"              # KV cache storage: "bf16", or "int8" (BS_FLAG_INT8_KV: about half the cache bytes)
     score: bool = False           # the scoring task: each prompt's log-likelihood and perplexity, one pass a sample
+    speculate: int = 0            # speculative decoding: tokens drafted per verify pass (0 = off; one GPU only)
+    draft: str = "ngram"          # the drafter: "ngram" (prompt lookup) or a draft model's name (same vocabulary)
 
     def __post_init__(self):
         if self.kv not in ("bf16", "int8"):
             raise ValueError(f"kv must be 'bf16' or 'int8' (got {self.kv!r})")
+        if self.speculate:
+            if not 1 <= self.speculate <= 7:
+                raise ValueError(f"speculate must be in [1, 7] (got {self.speculate}): a verify pass holds 8 positions")
+            if self.kv != "bf16":
+                raise ValueError("speculative decoding needs kv = 'bf16' (no verify pass over an int8 KV cache yet)")
+            if self.max_length <= 0:
+                raise ValueError("speculative decoding is a generation task: max_length must be > 0")
+            if self.score:
+                raise ValueError("speculative decoding and the scoring task exclude each other")
 
 
 def synthetic_prompts(cfg: RunConfig, vocab):
@@ -105,6 +122,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     lengths (None: synthetic).  Returns {"samples": [[max_length ids] per sample], ...} on rank 0,
     None elsewhere.  Collective: every rank calls it with the same cfg."""
     say = log if (log is not None and rank == 0) else (lambda *_: None)
+    if cfg.speculate and world != 1:
+        raise ValueError("speculative decoding runs on one stage (world == 1): acceptance is data-dependent, the "
+                         "pipeline's schedule is not")
     if cfg.num_sample < 1 or cfg.max_length < 0 or cfg.core_pool_size < 1:
         raise ValueError("num_sample and core_pool_size must be >= 1, max_length >= 0 (0: classification)")
     model = config.get(cfg.model) if isinstance(cfg.model, str) else cfg.model
@@ -127,6 +147,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
         return _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.max_length == 0:
         return _classify_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
+    if cfg.speculate:
+        return _spec_run(cfg, model, device, prompts, lens, say)
     # samples in flight = n_mb micro-batches x mb rows: one micro-batch per stage keeps every stage
     # busy; the rest of the pool rides as rows of a micro-batch (one GPU: one batched decode)
     n_mb = min(cfg.core_pool_size, world)
@@ -322,6 +344,48 @@ def _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory,
     ntok = sum(lens)
     res = {"samples": out, "task": "score", "num_sample": cfg.num_sample, "core_pool_size": cfg.core_pool_size,
            "stages": world, "prompt_lens": lens, "passes": len(passes), "seconds": dt, "tokens_per_s": ntok / dt}
+    say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
+    say(STATES[3], {})
+    return res
+
+
+def _spec_run(cfg, model, device, prompts, lens, say):
+    """--speculate K (world == 1): the whole model as one stage, the samples decoded one after another in KV row 0
+    by speculative.SpeculativeDecoder.  Returns the generation task's record plus the acceptance statistics."""
+    from .speculative import NgramDrafter, SpeculativeDecoder, StageDrafter
+    from .stage import Stage
+    dev = device.index if device.type == "cuda" and device.index is not None else 0
+    max_ctx = max(lens) + cfg.max_length + 1
+
+    def whole(m):
+        return Stage(m.hidden, m.n_head, m.n_layer, m.vocab, 0, m.n_layer, dtype=cfg.dtype, device=dev, max_batch=1,
+                     max_ctx=max_ctx, max_tokens=max(lens) + 32, seed=cfg.seed, int8_weights=m.int8_weights,
+                     mxfp4_weights=m.mxfp4_weights)
+
+    if cfg.draft == "ngram":
+        drafter = NgramDrafter(cfg.speculate)
+    else:
+        dm = config.get(cfg.draft) if isinstance(cfg.draft, str) else cfg.draft
+        if dm.vocab != model.vocab:
+            raise ValueError(f"draft model {dm.name} has another vocabulary ({dm.vocab}) than {model.name} ({model.vocab})")
+        drafter = StageDrafter([whole(dm)], cfg.speculate)
+    dec = SpeculativeDecoder([whole(model)], drafter, cfg.speculate)
+    say(STATES[0], {"rank_layers": [0, model.n_layer], "stages": 1, "speculate": cfg.speculate, "draft": cfg.draft})
+    say(STATES[1], {"num_sample": cfg.num_sample, "max_length": cfg.max_length})
+    out, tot = [], {"passes": 0, "drafted": 0, "accepted": 0, "plain_steps": 0}
+    t_start = time.perf_counter()
+    for p in prompts:
+        toks, st = dec.generate(p, cfg.max_length)
+        out.append(toks)
+        for k in tot:
+            tot[k] += st[k]
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t_start
+    res = {"samples": out, "num_sample": cfg.num_sample, "max_length": cfg.max_length,
+           "core_pool_size": cfg.core_pool_size, "stages": 1, "prompt_lens": lens, "seconds": dt,
+           "tokens_per_s": cfg.num_sample * cfg.max_length / dt, "speculate": cfg.speculate, "draft": cfg.draft, **tot,
+           "acceptance_rate": tot["accepted"] / tot["drafted"] if tot["drafted"] else None}
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
     say(STATES[3], {})
     return res

@@ -39,6 +39,7 @@ BS_WEIGHTS_SYNTHETIC = 0
 BS_WEIGHTS_HOST = 1
 BS_STEP_HOST_IO = 1
 BS_STEP_LOGITS = 2
+BS_STEP_VERIFY = 4        # bs_step.flags: short verify pass (2 <= seq <= 8), greedy ids at every position
 BS_FLAG_INT8_WEIGHTS = 1  # bs_stage_desc.flags: weight-only int8 block matrices
 BS_FLAG_CLASSIFIER = 2    # bs_stage_desc.flags: sequence-classification tail (score head, class ids out)
 BS_FLAG_INT8_KV = 4       # bs_stage_desc.flags: int8 KV cache, one fp32 scale per (position, head) vector
@@ -266,10 +267,14 @@ class Stage:
         return st, pasts
 
     # ---- fast path (device pointers, stream ordered)
-    def forward(self, inp, out, batch, seq, slot=0, past_len=None, logits=None, stream=None):
+    def forward(self, inp, out, batch, seq, slot=0, past_len=None, logits=None, stream=None, verify=False):
         """past_len: positions already cached, one int for every row or one per row (None: the
-        host mirror of each row's position)."""
-        st, pasts = self._step(batch, seq, slot, past_len, BS_STEP_LOGITS if logits is not None else 0)
+        host mirror of each row's position).
+        verify: a BS_STEP_VERIFY pass (2 <= seq <= 8, batch * seq <= 32): the last stage writes int32 ids
+        [batch][seq], the greedy token of every position (logits: fp32 [batch][seq][vocab]); on device buffers it
+        replays a captured graph like a decode step."""
+        flags = (BS_STEP_LOGITS if logits is not None else 0) | (BS_STEP_VERIFY if verify else 0)
+        st, pasts = self._step(batch, seq, slot, past_len, flags)
         _check(self._fwd(self._h, ctypes.byref(st), _ptr(inp), _ptr(out), _ptr(logits), stream))
         if pasts is None:
             self.past[slot:slot + batch] = [st.past_len + seq] * batch
@@ -353,14 +358,16 @@ class Stage:
         _check(lib().bs_head_slice(self._h, _ptr(xn), batch, _ptr(keys_in), _ptr(keys_out), _ptr(tokens), stream))
 
     # ---- host I/O convenience (numpy in, numpy out)
-    def forward_host(self, x, batch, seq, slot=0, past_len=None, want_logits=False):
+    def forward_host(self, x, batch, seq, slot=0, past_len=None, want_logits=False, verify=False):
+        """verify: a BS_STEP_VERIFY pass; the last stage returns ids [batch][seq] (and logits [batch][seq][vocab])."""
         if self.is_first:
             x = np.ascontiguousarray(x, dtype=np.int32).reshape(batch, seq)
         else:
             x = np.ascontiguousarray(x, dtype=np.float32).reshape(batch, seq, self.hidden)
-        out = np.empty(batch, np.int32) if self.is_last else np.empty((batch, seq, self.hidden), np.float32)
-        logits = np.empty((batch, self.n_out), np.float32) if want_logits else None
-        flags = BS_STEP_HOST_IO | (BS_STEP_LOGITS if want_logits else 0)
+        rows = (batch, seq) if verify else (batch,)
+        out = np.empty(rows, np.int32) if self.is_last else np.empty((batch, seq, self.hidden), np.float32)
+        logits = np.empty(rows + (self.n_out,), np.float32) if want_logits else None
+        flags = BS_STEP_HOST_IO | (BS_STEP_LOGITS if want_logits else 0) | (BS_STEP_VERIFY if verify else 0)
         st, pasts = self._step(batch, seq, slot, past_len, flags)
         _check(lib().bs_forward(self._h, ctypes.byref(st), x.ctypes.data, out.ctypes.data,
                                 logits.ctypes.data if logits is not None else None, None))
@@ -370,6 +377,14 @@ class Stage:
             for i, r in enumerate(range(slot, slot + batch)):
                 self.past[r] = pasts[i] + seq
         return (out, logits) if want_logits else out
+
+    def rollback(self, slot, pos):
+        """Forget the positions of KV row `slot` at and beyond `pos` (speculative decoding: the rejected drafts).
+        Only the host mirror moves: positions are passed per call, and no kernel reads a cache entry at or beyond
+        its row's position."""
+        if not 0 <= pos <= self.past[slot]:
+            raise BloomStageError(f"rollback of row {slot} to {pos}: it holds {self.past[slot]} positions")
+        self.past[slot] = pos
 
     def reset(self, slot=-1):
         _check(lib().bs_reset_kv(self._h, slot))

@@ -161,6 +161,26 @@ typedef struct bs_step {
 
 #define BS_STEP_HOST_IO 1  /* in/out/logits are host pointers (copied in/out, stream-synchronous) */
 #define BS_STEP_LOGITS 2   /* last stage also writes fp32 logits [B][vocab] of each row's last position */
+/* step->flags.  BS_STEP_VERIFY (bs_forward, every stage of a generation model): a short pass of 2 <= seq <= 8 new
+ * tokens per row with batch * seq <= 32 (BS_ERR_INVALID otherwise) over a warm cache -- the verify step of speculative
+ * decoding: the row is fed [last token, draft_1 .. draft_k] and the greedy token of EVERY position comes back.
+ *   in : as any forward.  out: a non-last stage writes fp32 hidden [B][S][hidden] as always; the last stage writes
+ *        int32 ids [B][S], entry (b, t) = the first index of the largest logit of position past_b + t (the greedy
+ *        rule).  logits (BS_STEP_LOGITS): fp32 [B][S][vocab].  BS_STEP_HOST_IO as for any forward.
+ *   The pass appends S positions to the KV rows and its last kernel advances the device copy of each row's position
+ *   by S, as every forward does.  Rolling a row back is the caller passing a smaller past_lens next time: a cache
+ *   entry at or beyond a row's position is never read, by this pass or any other, so rejected drafts need no cleanup.
+ *   The linears are the unflagged pass's (batched GEMVs on M = B * S rows; BS_FLAG_INT8_WEIGHTS and
+ *   BS_FLAG_MXFP4_WEIGHTS stages work), so the K / V rows written equal the unflagged pass's of the same shape bit
+ *   for bit; the attention is a short-query split-context kernel on a grid that is a static function of (B, n_head,
+ *   max_ctx), the tail scores all B * S positions with the exact head (never screened:
+ *   bs_read_head_screen reports *count = -1).  Results are bit-identical from run to run.  On device buffers the pass
+ *   is captured and replayed like a decode step (bs_set_graphs).
+ *   The first verify call allocates the attention's split partials and the per-position keys (counted under
+ *   workspace_bytes from then on).
+ *   BS_ERR_UNSUPPORTED on a BS_FLAG_INT8_KV stage; BS_ERR_STATE on a classifier stage, after bs_set_sampling chose
+ *   top_k > 1, and on a last stage without the whole lm_head.  bs_forward_score rejects the flag (BS_ERR_INVALID). */
+#define BS_STEP_VERIFY 4
 
 /* Create a stage on desc->device: allocates weights, KV cache and workspace in HBM. */
 int bs_init_stage(const bs_stage_desc *desc, bs_stage **out);
@@ -244,7 +264,7 @@ int bs_head_slice(bs_stage *stage, const void *xn, int32_t batch, const uint64_t
  *   base_seed ^ request_id, set before the request's first sampled step). */
 int bs_set_sampling(bs_stage *stage, int32_t top_k, float temperature, uint64_t seed);
 
-/* Decode steps (S = 1) on device buffers are captured once per shape into a hipGraph and replayed
+/* Decode steps (S = 1) and BS_STEP_VERIFY passes on device buffers are captured once per shape into a hipGraph and replayed
  * (the default, on = 1); on = 0 launches them eagerly every step (same kernels, same results: for
  * debugging and A/B timing).  Drops captured graphs.  Returns BS_OK.  A stage starts with graphs off
  * when the environment holds BS_GRAPHS=0 at bs_init_stage (rocprofv3 --pmc runs). */
