@@ -200,43 +200,38 @@ void launch_set_past(int* past_dev, const int* values, int n, hipStream_t s);
 void launch_quantize_rows(const void* W_bf16, int8_t* Q, float* scale, int N, int K, hipStream_t s);
 // out bf16 [N][K] = Q * scale (row-wise).
 void launch_dequant_rows(const int8_t* Q, const float* scale, void* out_bf16, int N, int K, hipStream_t s);
-// Does launch_linear_q8 run M rows of a K-wide GEMV straight from the int8 weights?
-bool linear_q8_gemv(int M, int K);
-// X bf16 [M][K] x (Q * scale)^T with epilogue (not EPI_ARGMAX).  M <= 8: int8 GEMV; otherwise Q is
-// dequantized into w_scratch (bf16, N*K) and the bf16 GEMM runs on it.
-void launch_linear_q8(const void* X, const int8_t* Q, const float* scale, void* w_scratch, int M, int N, int K,
-                      const Epi& ep, hipStream_t s);
-// The int8 dense GEMV on ctx = merge(split-attention partials) (M <= 2): the int8 counterpart of
-// launch_linear_parts.
-bool linear_q8_parts_supported(int M, int K, int head_dim, int nsplit);
-void launch_linear_q8_parts(const AttnParts& p, const int8_t* Q, const float* scale, int M, int N, int K,
-                            const Epi& ep, hipStream_t s);
-// M <= 4, K <= 4096: LayerNorm(x rows) fused into the int8 GEMV prologue (rows normalised to LDS).
-bool linear_q8_ln_fused(int M, int K);
-void launch_linear_q8_ln(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
-                         float eps, const int8_t* Q, const float* scale, int M, int N, int K, const Epi& ep,
-                         hipStream_t s);
 // ---- Weight-only MXFP4 (bf16 stages with BS_FLAG_MXFP4_WEIGHTS; kernels.hip "Weight-only MXFP4") ----
 // W bf16 [N][K], K % 32 == 0 -> E2M1 codes Q (N * K / 2 bytes, 16-B block records) + E8M0 scales SC [N][K / 32]
 // by the rule of include/bloomstage.h.
 void launch_quantize_mx4(const void* W_bf16, uint8_t* Q, uint8_t* SC, int N, int K, hipStream_t s);
 // out bf16 [N][K] = the dequantised weights (exact in bf16).
 void launch_dequant_mx4(const uint8_t* Q, const uint8_t* SC, void* out_bf16, int N, int K, hipStream_t s);
-// Does launch_linear_mx4 run M rows of an N x K matrix straight from the fp4 codes?
-bool linear_mx4_gemv(int M, int N, int K);
-// X bf16 [M][K] x dequant(Q, SC)^T with epilogue (not EPI_ARGMAX).  linear_mx4_gemv(M, N, K): fp4 GEMV;
-// otherwise the weights are dequantised into w_scratch (bf16, N*K) and the bf16 GEMM runs on them.
-void launch_linear_mx4(const void* X, const uint8_t* Q, const uint8_t* SC, void* w_scratch, int M, int N, int K,
-                       const Epi& ep, hipStream_t s);
-// The fp4 dense GEMV on ctx = merge(split-attention partials) (M <= 2).
-bool linear_mx4_parts_supported(int M, int K, int head_dim, int nsplit);
-void launch_linear_mx4_parts(const AttnParts& p, const uint8_t* Q, const uint8_t* SC, int M, int N, int K,
-                             const Epi& ep, hipStream_t s);
-// M <= 4, K <= 4096: LayerNorm(x rows) fused into the fp4 GEMV prologue.
-bool linear_mx4_ln_fused(int M, int K);
-void launch_linear_mx4_ln(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
-                          float eps, const uint8_t* Q, const uint8_t* SC, int M, int N, int K, const Epi& ep,
-                          hipStream_t s);
+
+// ---- A block matrix as the stage holds it ----
+// w: T [N][K] and both scales null; or int8 [N][K] with row_scale fp32 [N] (weight-only int8); or MXFP4 code
+// records with blk_scale E8M0 [N][K / 32] (weight-only MXFP4).  The quantised formats belong to bf16 stages and
+// never take EPI_ARGMAX (the tied lm_head stays bf16).  Epi::col_scale is set by the launches.
+struct WMat {
+  const void* w;
+  const float* row_scale = nullptr;
+  const uint8_t* blk_scale = nullptr;
+};
+// Does launch_wmat stream the stored weights for M rows (a decode GEMV, bound by wmat_stream_bytes), or run a
+// GEMM (MXFP4 beyond its GEMV shapes and quantised prefill: on the weights dequantised into w_scratch)?
+bool wmat_streams(int is_bf16, const WMat& w, int M, int N, int K);
+// Weight and scale bytes of the matrix as a decode GEMV streams them.
+double wmat_stream_bytes(const WMat& w, int N, int K, size_t esz);
+// X (T; bf16 for a quantised w) [M][K] x W^T with epilogue; w_scratch: bf16 [N][K] for the dequantised weights.
+void launch_wmat(int is_bf16, const void* X, const WMat& w, void* w_scratch, int M, int N, int K, const Epi& ep,
+                 hipStream_t s);
+// Does launch_wmat_ln take these rows?  Unquantised: always (launch_linear_ln).  Quantised: M <= 4, K <= 4096, the
+// LayerNorm fused into the GEMV prologue; otherwise the caller runs launch_ln_rows, then launch_wmat.
+bool wmat_takes_ln(const WMat& w, int M, int K);
+void launch_wmat_ln(int is_bf16, const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
+                    float eps, void* xn_scratch, const WMat& w, int M, int N, int K, const Epi& ep, hipStream_t s);
+// The dense GEMV on ctx = merge(split-attention partials): can it run M rows of a K-wide ctx split `nsplit` ways?
+bool wmat_parts_supported(const WMat& w, int M, int K, int head_dim, int nsplit);
+void launch_wmat_parts(const AttnParts& p, const WMat& w, int M, int N, int K, const Epi& ep, hipStream_t s);
 // LayerNorm of M fp32 rows -> bf16 (register-resident one-block-per-row kernel when K <= 4096).
 void launch_ln_rows(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta, float eps,
                     void* out_bf16, int M, int K, hipStream_t s);

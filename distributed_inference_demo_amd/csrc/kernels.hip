@@ -556,6 +556,110 @@ __device__ __forceinline__ void ln_rows_finish(const LnArgs& ln, int M, int K, f
   __syncthreads();
 }
 
+// The activation prologue and the tail shared by the decode GEMVs on quantised weights (gemv_q8_body, gemv_mx4_body).
+// The activations are one of: LayerNorm(ln rows) (LN), the merged split-attention partials (PARTS; attn_merge.h),
+// plain X staged in LDS (XL), or plain X read from global memory.  Loads return in order, so whatever the prologue
+// reads goes out BEFORE the weight stream (gemv_act_issue) -- issued behind it, it would wait for all of it -- and
+// is turned into bf16 rows in LDS while the weight loads fly (gemv_act_finish).  The registers in between:
+template <int MM, bool LN, bool XL>
+struct GemvActRegs {
+  PartsRegs pr;                // PARTS: the thread's first group of partials
+  float4 xv[LN ? MM : 1][4];   // LN: the rows, their shift constants and gamma / beta
+  float cc[LN ? MM : 1];
+  uint2 gb[4][2];
+  u16x8 xpre[XL ? 4 : 1];      // XL: up to 4 16-B pieces of X per thread
+};
+
+struct PartsLd1 { __device__ float operator()(const float* p, size_t i) const { return p[i]; } };
+struct PartsLd4 {
+  __device__ float4 operator()(const float* p, size_t i) const { return *reinterpret_cast<const float4*>(p + i); }
+};
+
+template <int MM, bool LN, bool XL, bool PARTS>
+__device__ __forceinline__ void gemv_act_issue(const bf16* Xg, const LnArgs& ln, const AttnParts& pa,
+                                               int M, int K, GemvActRegs<MM, LN, XL>& a) {
+  if constexpr (PARTS) {  // group g = 4 context columns of one row
+    const int kq = K >> 2, g = min((int)threadIdx.x, M * kq - 1);
+    attn_parts_load(pa, g / kq, (g % kq) * 4, PartsLd1{}, PartsLd4{}, a.pr);
+  }
+  if constexpr (LN) {
+    if (threadIdx.x < 256) ln_rows_load<MM>(ln, M, K, a.xv, a.cc, a.gb);
+  }
+  if constexpr (XL) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int i = min((int)threadIdx.x + j * (int)blockDim.x, M * K / 8 - 1);
+      a.xpre[j] = reinterpret_cast<const u16x8*>(Xg)[i];
+    }
+  }
+}
+
+// -> the bf16 rows [M][K] the K loop reads: the block's dynamic LDS (M * K * 2 bytes) unless the activations are
+// plain X without XL.  `scratch`: 64 floats of LDS (LN).
+template <int MM, bool LN, bool XL, bool PARTS>
+__device__ __forceinline__ const bf16* gemv_act_finish(const bf16* Xg, const LnArgs& ln,
+                                                       const AttnParts& pa, int M, int K,
+                                                       GemvActRegs<MM, LN, XL>& a, float* scratch) {
+  extern __shared__ __align__(16) unsigned char gemv_act_lds[];
+  bf16* xl = reinterpret_cast<bf16*>(gemv_act_lds);
+  if constexpr (LN) {
+    ln_rows_finish<MM>(ln, M, K, a.xv, a.cc, a.gb, xl, scratch);
+    return xl;
+  } else if constexpr (PARTS) {  // merged context rows (bf16, the attn_decode_kernel rounding) to LDS
+    const int kq = K >> 2, ngroups = M * kq;
+    auto put = [&](int g, const PartsRegs& rr) {
+      float o[4];
+      attn_parts_combine(pa.nsplit, rr, o);
+      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+      bf16x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; j++) v[j] = (bf16)o[j];
+      *reinterpret_cast<bf16x4*>(xl + (size_t)(g / kq) * K + (g % kq) * 4) = v;
+    };
+    if ((int)threadIdx.x < ngroups) put(threadIdx.x, a.pr);
+    for (int g = threadIdx.x + blockDim.x; g < ngroups; g += blockDim.x) {
+      PartsRegs rr;
+      attn_parts_load(pa, g / kq, (g % kq) * 4, PartsLd1{}, PartsLd4{}, rr);
+      put(g, rr);
+    }
+    __syncthreads();
+    return xl;
+  } else if constexpr (XL) {  // plain X staged once per block in LDS (the block's waves share it; one L2 pass)
+    const int n16 = M * K / 8;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int i = threadIdx.x + j * blockDim.x;
+      if (i < n16) reinterpret_cast<u16x8*>(gemv_act_lds)[i] = a.xpre[j];
+    }
+    for (int i = threadIdx.x + 4 * blockDim.x; i < n16; i += blockDim.x)
+      reinterpret_cast<u16x8*>(gemv_act_lds)[i] = reinterpret_cast<const u16x8*>(Xg)[i];
+    __syncthreads();
+    return xl;
+  } else {
+    return Xg;
+  }
+}
+
+// Tail: the wave's lanes hold partial sums v[r][m] of weight rows n0 .. n0 + R - 1 against activation rows m < M;
+// lane r * MM + m keeps the reduced sum of (r, m) and stores it through the epilogue.  `lane` is the caller's
+// threadIdx.x & 63, handed in rather than recomputed (a second copy changes the int8 instances' register counts).
+template <int R, int MM, int KIND>
+__device__ __forceinline__ void gemv_reduce_store(const Epi& ep, int lane, int n0, int M, int N,
+                                                  const float (&v)[R][MM]) {
+  float mine = 0.f;
+#pragma unroll
+  for (int r = 0; r < R; r++)
+#pragma unroll
+    for (int m = 0; m < MM; m++) {
+      if (m < M) {
+        const float t = wave_sum(v[r][m]);
+        if (lane == r * MM + m) mine = t;
+      }
+    }
+  const int r = lane / MM, m = lane - r * MM;
+  if (lane < R * MM && m < M && n0 + r < N) epi_store<bf16, KIND>(ep, m, n0 + r, mine);
+}
+
 // LayerNorm of M fp32 rows (K <= 4096, K % 4 == 0) -> bf16 with WPR waves per row (a 64 * WPR-thread block): the row
 // in registers (NV float4 per lane; lane l of wave w holds float4 groups i * 64 * WPR + w * 64 + l), the shifted-sum
 // statistics of ln_rows_finish by DPP wave reductions, and for WPR > 1 one LDS exchange of the WPR wave sums (added in
@@ -3260,72 +3364,12 @@ __device__ __forceinline__ void gemv_q8_body(const int8_t* __restrict__ Q, const
         for (int w = 0; w < W; w++) wv[u][r][w] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wr[r] + c + 16 * w));
     }
   };
-  // PARTS: the split-attention partials (attn_merge.h) go out before the weights
-  const int kq = K >> 2, ngroups = M * kq;
-  PartsRegs pr[PARTS ? 1 : 1];
-  auto pld1 = [](const float* p, size_t i) { return p[i]; };
-  auto pld4 = [](const float* p, size_t i) { return *reinterpret_cast<const float4*>(p + i); };
-  if constexpr (PARTS) {
-    const int g = min((int)threadIdx.x, ngroups - 1);
-    attn_parts_load(pa, g / kq, (g % kq) * 4, pld1, pld4, pr[0]);
-  }
-  // LN: the rows (and gamma/beta) go out before the weights -- loads return in order, so rows issued
-  // behind the weight stream would wait for all of it -- and the block normalises them into LDS while
-  // the weight loads fly
-  float4 xv[LN ? MM : 1][4];
-  float cc[LN ? MM : 1];
-  uint2 gb[4][2];
-  if constexpr (LN) {
-    if (threadIdx.x < 256) ln_rows_load<MM>(ln, M, K, xv, cc, gb);
-  }
-  // XL: the plain X rows likewise go out ahead of the weights (up to 4 16-B pieces per thread)
-  constexpr int XP = XL ? 4 : 1;
-  u16x8 xpre[XP];
-  if constexpr (XL) {
-#pragma unroll
-    for (int j = 0; j < XP; j++) {
-      const int i = min((int)threadIdx.x + j * (int)blockDim.x, M * K / 8 - 1);
-      xpre[j] = reinterpret_cast<const u16x8*>(Xg)[i];
-    }
-  }
+  // the prologue's operands go out before the weights; the block turns them into bf16 rows while the weight loads fly
+  GemvActRegs<MM, LN, XL> act;
+  __shared__ float ln_scratch[64];
+  gemv_act_issue<MM, LN, XL, PARTS>(Xg, ln, pa, M, K, act);
   issue(c0);
-  extern __shared__ __align__(16) unsigned char q8_lds[];
-  const bf16* X = Xg;
-  if constexpr (LN) {
-    __shared__ float scratch[64];
-    ln_rows_finish<MM>(ln, M, K, xv, cc, gb, reinterpret_cast<bf16*>(q8_lds), scratch);
-    X = reinterpret_cast<const bf16*>(q8_lds);
-  } else if constexpr (PARTS) {  // merged context rows (bf16, the attn_decode_kernel rounding) to LDS
-    bf16* xl = reinterpret_cast<bf16*>(q8_lds);
-    auto put = [&](int g, const PartsRegs& rr) {
-      float o[4];
-      attn_parts_combine(pa.nsplit, rr, o);
-      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-      bf16x4 v;
-#pragma unroll
-      for (int j = 0; j < 4; j++) v[j] = (bf16)o[j];
-      *reinterpret_cast<bf16x4*>(xl + (size_t)(g / kq) * K + (g % kq) * 4) = v;
-    };
-    if ((int)threadIdx.x < ngroups) put(threadIdx.x, pr[0]);
-    for (int g = threadIdx.x + blockDim.x; g < ngroups; g += blockDim.x) {
-      PartsRegs rr;
-      attn_parts_load(pa, g / kq, (g % kq) * 4, pld1, pld4, rr);
-      put(g, rr);
-    }
-    __syncthreads();
-    X = xl;
-  } else if (XL) {  // plain X staged once per block in LDS (the block's waves share it; one L2 pass)
-    const int n16 = M * K / 8;
-#pragma unroll
-    for (int j = 0; j < XP; j++) {
-      const int i = threadIdx.x + j * blockDim.x;
-      if (i < n16) reinterpret_cast<u16x8*>(q8_lds)[i] = xpre[j];
-    }
-    for (int i = threadIdx.x + XP * blockDim.x; i < n16; i += blockDim.x)
-      reinterpret_cast<u16x8*>(q8_lds)[i] = reinterpret_cast<const u16x8*>(Xg)[i];
-    __syncthreads();
-    X = reinterpret_cast<const bf16*>(q8_lds);
-  }
+  const bf16* X = gemv_act_finish<MM, LN, XL, PARTS>(Xg, ln, pa, M, K, act, ln_scratch);
   for (int base = c0; base < K; base += UQ * STEP) {
     const bool more = base + UQ * STEP < K;
 #pragma unroll
@@ -3375,18 +3419,12 @@ __device__ __forceinline__ void gemv_q8_body(const int8_t* __restrict__ Q, const
       }
     }
   }
-  float mine = 0.f;
+  float v[R][MM];  // the offset form's correction per lane; ep.col_scale = scale is applied by the epilogue
 #pragma unroll
   for (int r = 0; r < R; r++)
 #pragma unroll
-    for (int m = 0; m < MM; m++) {
-      if (m < M) {
-        const float t = wave_sum((acc[r][m].x + acc[r][m].y) - 128.f * (xs[m].x + xs[m].y));
-        if (lane == r * MM + m) mine = t;
-      }
-    }
-  const int r = lane / MM, m = lane - r * MM;
-  if (lane < R * MM && m < M && n0 + r < N) epi_store<bf16, KIND>(ep, m, n0 + r, mine);  // ep.col_scale = scale
+    for (int m = 0; m < MM; m++) v[r][m] = (acc[r][m].x + acc[r][m].y) - 128.f * (xs[m].x + xs[m].y);
+  gemv_reduce_store<R, MM, KIND>(ep, lane, n0, M, N, v);
 }
 
 // WIDE: one block of up to 16 waves per CU (the rows GEMV's per-CU geometry, rows_geometry): the
@@ -3405,8 +3443,7 @@ __global__ __launch_bounds__(WIDE ? 1024 : 256) void gemv_q8_kernel(const int8_t
 template <int R, int MM, bool LN = false, bool PARTS = false>
 static void gemv_q8_launch(const int8_t* Q, const float* scale, const bf16* X, const LnArgs& ln, int M, int N, int K,
                            const Epi& ep, hipStream_t s, const AttnParts& pa = AttnParts{}) {
-  const size_t shm = (LN || PARTS) ? (size_t)M * K * sizeof(bf16) : 0;
-  const int blocks = (N + 4 * R - 1) / (4 * R);
+  const size_t xbytes = (size_t)M * K * sizeof(bf16);
   // steps of every row in flight: the whole row (<= 8 steps of 64 x 16 B) for matrices up to 12 M weights,
   // where the grid is a few waves per SIMD and latency decides (bloom-1b1 int8 B=1: 1207 -> 1221 tok/s);
   // one step beyond, where the stream is bandwidth-bound and deeper queues only cost occupancy
@@ -3414,78 +3451,48 @@ static void gemv_q8_launch(const int8_t* Q, const float* scale, const bf16* X, c
   const int steps = (K + 1023) / 1024;
   const int uq = (size_t)N * K > (12u << 20) ? 1 : min(steps <= 2 ? 2 : steps <= 4 ? 4 : steps <= 6 ? 6 : 8, R >= 4 ? 4 : 8);
   // plain X staged in LDS (loaded ahead of the weights) by the wide blocks when it fits 64 KB
-  const bool wide_xl = (size_t)M * K * sizeof(bf16) <= 65536;
+  const bool wide_xl = xbytes <= 65536;
+  auto go = [&](auto rc, auto xl, auto wide, int blocks, int threads) {
+    constexpr int RW = decltype(rc)::value;
+    constexpr bool XL = decltype(xl)::value != 0, WIDE = decltype(wide)::value != 0;
+    const size_t shm = (LN || PARTS || XL) ? xbytes : 0;
+    auto gu = [&](auto uc) {
+      constexpr int UQ = decltype(uc)::value;
+      gemv_q8_kernel<RW, MM, LN, 16, XL, UQ, PARTS, WIDE><<<blocks, threads, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
+    };
+    if (uq == 1) gu(EpiKindC<1>{});  // one step in flight
+    else if (uq <= 2) gu(EpiKindC<2>{});
+    else if (uq <= 4) gu(EpiKindC<4>{});
+    else if (WIDE || uq <= 6) gu(EpiKindC<6>{});  // the wide blocks take uq <= 6 only
+    else if constexpr (!WIDE) gu(EpiKindC<8>{});
+  };
   if constexpr (MM == 1 && R <= 2) {
     int rr = 0, waves = 0;
     rows_geometry(N, K, M, R, &rr, &waves);
     // matrices up to 32 M weights (bloom-1b1 int8 B=1 1206 -> 1281 tok/s, 560m 1685 -> 1768, 3b 735 -> 762;
     // bloom-7b1's 50-67 M-weight QKV / fc1 / fc2 keep 4-wave blocks; profiles/r02_q8_uq_ab.txt)
     if ((size_t)N * K <= (32u << 20) && rr <= 2 && waves >= 4 && uq <= 6) {
-      auto go = [&](auto rc) {
+      auto gw = [&](auto rc) {
         constexpr int RW = decltype(rc)::value;
         const int wb = (N + waves * RW - 1) / (waves * RW);
-        const dim3 g(wb), t(waves * 64);
         if constexpr (!LN && !PARTS) {
           if (wide_xl) {  // plain X staged in LDS, loaded ahead of the weights
-            const size_t shx = (size_t)M * K * sizeof(bf16);
-            if (uq == 1) gemv_q8_kernel<RW, 1, false, 16, true, 1, false, true><<<g, t, shx, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-            else if (uq <= 2) gemv_q8_kernel<RW, 1, false, 16, true, 2, false, true><<<g, t, shx, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-            else if (uq <= 4) gemv_q8_kernel<RW, 1, false, 16, true, 4, false, true><<<g, t, shx, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-            else gemv_q8_kernel<RW, 1, false, 16, true, 6, false, true><<<g, t, shx, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
+            go(rc, EpiKindC<1>{}, EpiKindC<1>{}, wb, waves * 64);
             return;
           }
         }
-        if (uq == 1) gemv_q8_kernel<RW, 1, LN, 16, false, 1, PARTS, true><<<g, t, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-        else if (uq <= 2) gemv_q8_kernel<RW, 1, LN, 16, false, 2, PARTS, true><<<g, t, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-        else if (uq <= 4) gemv_q8_kernel<RW, 1, LN, 16, false, 4, PARTS, true><<<g, t, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-        else gemv_q8_kernel<RW, 1, LN, 16, false, 6, PARTS, true><<<g, t, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
+        go(rc, EpiKindC<0>{}, EpiKindC<1>{}, wb, waves * 64);
       };
-      if (rr == 2) go(EpiKindC<2>{});
-      else go(EpiKindC<1>{});
+      if (rr == 2) gw(EpiKindC<2>{});
+      else gw(EpiKindC<1>{});
       return;
     }
   }
-  if (uq == 1) {  // one step in flight
-    gemv_q8_kernel<R, MM, LN, 16, false, 1, PARTS><<<blocks, 256, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-  } else if (uq <= 2) {
-    gemv_q8_kernel<R, MM, LN, 16, false, 2, PARTS><<<blocks, 256, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-  } else if (uq <= 4) {
-    gemv_q8_kernel<R, MM, LN, 16, false, 4, PARTS><<<blocks, 256, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-  } else if (uq <= 6) {
-    gemv_q8_kernel<R, MM, LN, 16, false, 6, PARTS><<<blocks, 256, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-  } else {
-    gemv_q8_kernel<R, MM, LN, 16, false, 8, PARTS><<<blocks, 256, shm, s>>>(Q, scale, X, ln, pa, M, N, K, ep);
-  }
+  go(EpiKindC<R>{}, EpiKindC<0>{}, EpiKindC<0>{}, (N + 4 * R - 1) / (4 * R), 256);
 }
 
-bool linear_q8_gemv(int M, int K) { return M >= 1 && M <= 8 && K % 32 == 0; }
-
-// Rows per wave of the int8 GEMV: 2 (profiles/r01_q8_rows_sweep.txt: 1b1 B=1 1128 -> 1177 tok/s against 1 row
-// below N = 8192, 7b1 equal).
-bool linear_q8_ln_fused(int M, int K) { return M >= 1 && M <= 4 && K % 32 == 0 && K <= 4096; }
-
-void launch_linear_q8_ln(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
-                         float eps, const int8_t* Q, const float* scale, int M, int N, int K, const Epi& ep,
-                         hipStream_t s) {
-  Epi e = ep;
-  e.col_scale = scale;
-  const LnArgs ln{x, row_stride, row_offset, (const bf16*)gamma, (const bf16*)beta, eps};
-  if (M <= 1) gemv_q8_launch<2, 1, true>(Q, scale, nullptr, ln, M, N, K, e, s);
-  else if (M <= 2) gemv_q8_launch<2, 2, true>(Q, scale, nullptr, ln, M, N, K, e, s);
-  else gemv_q8_launch<2, 4, true>(Q, scale, nullptr, ln, M, N, K, e, s);
-}
-
-bool linear_q8_parts_supported(int M, int K, int head_dim, int nsplit) {
-  return M >= 1 && M <= 2 && K % 32 == 0 && K <= 4096 && head_dim % 4 == 0 && nsplit >= 2 && nsplit <= kPartsMaxSplit;
-}
-
-void launch_linear_q8_parts(const AttnParts& p, const int8_t* Q, const float* scale, int M, int N, int K,
-                            const Epi& ep, hipStream_t s) {
-  Epi e = ep;
-  e.col_scale = scale;
-  if (M <= 1) gemv_q8_launch<2, 1, false, true>(Q, scale, nullptr, LnArgs{}, M, N, K, e, s, p);
-  else gemv_q8_launch<2, 2, false, true>(Q, scale, nullptr, LnArgs{}, M, N, K, e, s, p);
-}
+// Does the int8 GEMV take M rows of a K-wide matrix?
+static bool linear_q8_gemv(int M, int K) { return M >= 1 && M <= 8 && K % 32 == 0; }
 
 void launch_quantize_rows(const void* W_bf16, int8_t* Q, float* scale, int N, int K, hipStream_t s) {
   if (N > 0) quantize_rows_kernel<<<N, 256, 0, s>>>((const bf16*)W_bf16, Q, scale, K);
@@ -3505,29 +3512,6 @@ void launch_ln_rows(const float* x, int row_stride, int row_offset, const void* 
   } else {
     launch_layernorm(1, x, nullptr, row_stride, row_offset, gamma, beta, out_bf16, 0, M, K, eps, s);
   }
-}
-
-void launch_linear_q8(const void* X, const int8_t* Q, const float* scale, void* w_scratch, int M, int N, int K,
-                      const Epi& ep, hipStream_t s) {
-  if (M <= 0) return;
-  if (ep.kind == EPI_ARGMAX) abort();  // the tied lm_head stays bf16
-  const bf16* x = (const bf16*)X;
-  Epi e = ep;
-  e.col_scale = scale;
-  // batched decode (4 < M <= 32): the int8 gemv_ldsw4 / tile GEMV converts in registers (no dequant pass);
-  // at M = 8 it reads the weights once where gemv_q8 re-reads activations per row (bloom-7b1 int8 B=8)
-  if (M > 4 && M <= 32 && gemv_tiles_dispatch<int8_t>(x, Q, M, N, K, e, s)) return;
-  if (linear_q8_gemv(M, K)) {
-    const LnArgs ln{};
-    if (M <= 1) gemv_q8_launch<2, 1>(Q, scale, x, ln, M, N, K, e, s);
-    else if (M <= 2) gemv_q8_launch<2, 2>(Q, scale, x, ln, M, N, K, e, s);
-    else if (M <= 4) gemv_q8_launch<2, 4>(Q, scale, x, ln, M, N, K, e, s);
-    else gemv_q8_launch<1, 8>(Q, scale, x, ln, M, N, K, e, s);
-    return;
-  }
-  // prefill: dequantize to the bf16 scratch, then the bf16 GEMM
-  launch_dequant_rows(Q, nullptr, w_scratch, N, K, s);
-  launch_linear(1, X, w_scratch, M, N, K, e, s);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3643,69 +3627,13 @@ __device__ __forceinline__ void gemv_mx4_body(const uint8_t* __restrict__ Q, con
       sv[u][r] = sr[r][b];
     }
   };
-  // prologue operands go out before the weights (loads return in order), as in gemv_q8_body
-  const int kq = K >> 2, ngroups = M * kq;
-  PartsRegs pr[1];
-  auto pld1 = [](const float* p, size_t i) { return p[i]; };
-  auto pld4 = [](const float* p, size_t i) { return *reinterpret_cast<const float4*>(p + i); };
-  if constexpr (PARTS) {
-    const int g = min((int)threadIdx.x, ngroups - 1);
-    attn_parts_load(pa, g / kq, (g % kq) * 4, pld1, pld4, pr[0]);
-  }
-  float4 xv[LN ? MM : 1][4];
-  float cc[LN ? MM : 1];
-  uint2 gb[4][2];
-  if constexpr (LN) {
-    if (threadIdx.x < 256) ln_rows_load<MM>(ln, M, K, xv, cc, gb);
-  }
-  constexpr int XP = XL ? 4 : 1;
-  u16x8 xpre[XP];
-  if constexpr (XL) {
-#pragma unroll
-    for (int j = 0; j < XP; j++) {
-      const int i = min((int)threadIdx.x + j * (int)blockDim.x, M * K / 8 - 1);
-      xpre[j] = reinterpret_cast<const u16x8*>(Xg)[i];
-    }
-  }
+  // the prologue's operands go out before the weights; the block turns them into bf16 rows while the weight loads fly
+  GemvActRegs<MM, LN, XL> act;
+  __shared__ float ln_scratch[64];
+  gemv_act_issue<MM, LN, XL, PARTS>(Xg, ln, pa, M, K, act);
 #pragma unroll
   for (int u = 0; u < UQ; u++) load(u, lane + 64 * u);
-  extern __shared__ __align__(16) unsigned char mx4_lds[];
-  const bf16* X = Xg;
-  if constexpr (LN) {
-    __shared__ float scratch[64];
-    ln_rows_finish<MM>(ln, M, K, xv, cc, gb, reinterpret_cast<bf16*>(mx4_lds), scratch);
-    X = reinterpret_cast<const bf16*>(mx4_lds);
-  } else if constexpr (PARTS) {  // merged context rows (bf16, the attn_decode_kernel rounding) to LDS
-    bf16* xl = reinterpret_cast<bf16*>(mx4_lds);
-    auto put = [&](int g, const PartsRegs& rr) {
-      float o[4];
-      attn_parts_combine(pa.nsplit, rr, o);
-      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-      bf16x4 v;
-#pragma unroll
-      for (int j = 0; j < 4; j++) v[j] = (bf16)o[j];
-      *reinterpret_cast<bf16x4*>(xl + (size_t)(g / kq) * K + (g % kq) * 4) = v;
-    };
-    if ((int)threadIdx.x < ngroups) put(threadIdx.x, pr[0]);
-    for (int g = threadIdx.x + blockDim.x; g < ngroups; g += blockDim.x) {
-      PartsRegs rr;
-      attn_parts_load(pa, g / kq, (g % kq) * 4, pld1, pld4, rr);
-      put(g, rr);
-    }
-    __syncthreads();
-    X = xl;
-  } else if constexpr (XL) {  // plain X staged once per block in LDS
-    const int n16 = M * K / 8;
-#pragma unroll
-    for (int j = 0; j < XP; j++) {
-      const int i = threadIdx.x + j * blockDim.x;
-      if (i < n16) reinterpret_cast<u16x8*>(mx4_lds)[i] = xpre[j];
-    }
-    for (int i = threadIdx.x + XP * blockDim.x; i < n16; i += blockDim.x)
-      reinterpret_cast<u16x8*>(mx4_lds)[i] = reinterpret_cast<const u16x8*>(Xg)[i];
-    __syncthreads();
-    X = reinterpret_cast<const bf16*>(mx4_lds);
-  }
+  const bf16* X = gemv_act_finish<MM, LN, XL, PARTS>(Xg, ln, pa, M, K, act, ln_scratch);
   const int rot = (lane >> 2) & 3;
   for (int sb = 0; sb < nb; sb += 64 * UQ) {
     const bool more = sb + 64 * UQ < nb;
@@ -3750,18 +3678,7 @@ __device__ __forceinline__ void gemv_mx4_body(const uint8_t* __restrict__ Q, con
       }
     }
   }
-  float mine = 0.f;
-#pragma unroll
-  for (int r = 0; r < R; r++)
-#pragma unroll
-    for (int m = 0; m < MM; m++) {
-      if (m < M) {
-        const float t = wave_sum(acc[r][m]);
-        if (lane == r * MM + m) mine = t;
-      }
-    }
-  const int r = lane / MM, m = lane - r * MM;
-  if (lane < R * MM && m < M && n0 + r < N) epi_store<bf16, KIND>(ep, m, n0 + r, mine);
+  gemv_reduce_store<R, MM, KIND>(ep, lane, n0, M, N, acc);
 }
 
 template <int R, int MM, bool LN, bool XL, int UQ, bool PARTS>
@@ -3811,53 +3728,100 @@ static void gemv_mx4_launch(const uint8_t* Q, const uint8_t* SC, const bf16* X, 
 // matrices) -- the 8-row instance re-reads 8 activation rows per weight row, from LDS on narrow models (+19..30 %
 // at h 1024 / 1536) but from L2 on wide ones (-14 % at h 2560 / 4096); above 8 rows never (passes of 8 rows lose at
 // every width, 1.3x at 16 rows to 3.7x at 32).
-bool linear_mx4_gemv(int M, int N, int K) {
+static bool linear_mx4_gemv(int M, int N, int K) {
   return M >= 1 && K % 32 == 0 && (M <= 4 || (M <= 8 && std::min(N, K) <= 2048));
 }
 
-bool linear_mx4_ln_fused(int M, int K) { return M >= 1 && M <= 4 && K % 32 == 0 && K <= 4096; }
+// ------------------------------------------------------------------------------------
+// A block matrix as the stage holds it (WMat, kernels.h): the one place that tells the weight formats apart.
+// Unquantised matrices go to launch_linear / launch_linear_ln / launch_linear_parts as they are.
+// ------------------------------------------------------------------------------------
+static bool wmat_quantised(const WMat& w) { return w.row_scale || w.blk_scale; }
 
-void launch_linear_mx4_ln(const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
-                          float eps, const uint8_t* Q, const uint8_t* SC, int M, int N, int K, const Epi& ep,
-                          hipStream_t s) {
-  Epi e = ep;
-  e.col_scale = nullptr;
-  const LnArgs ln{x, row_stride, row_offset, (const bf16*)gamma, (const bf16*)beta, eps};
-  if (M <= 1) gemv_mx4_launch<2, 1, true>(Q, SC, nullptr, ln, M, N, K, e, s);
-  else if (M <= 2) gemv_mx4_launch<2, 2, true>(Q, SC, nullptr, ln, M, N, K, e, s);
-  else gemv_mx4_launch<2, 4, true>(Q, SC, nullptr, ln, M, N, K, e, s);
+// M (<= MAXM) activation rows -> the <R weight rows per wave, MM rows> instance of a quantised GEMV.
+// Rows per wave of the int8 GEMV: 2 (profiles/r01_q8_rows_sweep.txt: 1b1 B=1 1128 -> 1177 tok/s against 1 row
+// below N = 8192, 7b1 equal).
+template <int MAXM, class F>
+static void gemv_wq_shape(int M, F&& go) {
+  if (M <= 1) go(EpiKindC<2>{}, EpiKindC<1>{});
+  else if (MAXM <= 2 || M <= 2) go(EpiKindC<2>{}, EpiKindC<2>{});
+  else if constexpr (MAXM > 2) {
+    if (MAXM <= 4 || M <= 4) go(EpiKindC<2>{}, EpiKindC<4>{});
+    else if constexpr (MAXM > 4) go(EpiKindC<1>{}, EpiKindC<8>{});
+  }
 }
 
-bool linear_mx4_parts_supported(int M, int K, int head_dim, int nsplit) {
+// The quantised GEMV on plain X (M <= 8), on LN(ln rows) (M <= 4) or on the merged partials pa (M <= 2).
+template <bool LN, bool PARTS>
+static void gemv_wq_launch(const WMat& w, const bf16* X, const LnArgs& ln, const AttnParts& pa, int M, int N, int K,
+                           const Epi& ep, hipStream_t s) {
+  Epi e = ep;
+  e.col_scale = w.row_scale;  // int8: the row scales; MXFP4: none (the conversion applies the block scales)
+  gemv_wq_shape<PARTS ? 2 : LN ? 4 : 8>(M, [&](auto rc, auto mc) {
+    constexpr int R = decltype(rc)::value, MM = decltype(mc)::value;
+    if (w.blk_scale) gemv_mx4_launch<R, MM, LN, PARTS>((const uint8_t*)w.w, w.blk_scale, X, ln, M, N, K, e, s, pa);
+    else gemv_q8_launch<R, MM, LN, PARTS>((const int8_t*)w.w, w.row_scale, X, ln, M, N, K, e, s, pa);
+  });
+}
+
+bool wmat_streams(int is_bf16, const WMat& w, int M, int N, int K) {
+  if (w.blk_scale) return linear_mx4_gemv(M, N, K);
+  return is_bf16 && M <= 32;  // int8: the tile GEMV or the int8 GEMV (a K % 32 != 0 matrix is dequantised all the same)
+}
+
+bool wmat_takes_ln(const WMat& w, int M, int K) {
+  return !wmat_quantised(w) || (M >= 1 && M <= 4 && K % 32 == 0 && K <= 4096);
+}
+
+bool wmat_parts_supported(const WMat& w, int M, int K, int head_dim, int nsplit) {
+  if (!wmat_quantised(w)) return linear_parts_supported(M, K, head_dim, nsplit);
   return M >= 1 && M <= 2 && K % 32 == 0 && K <= 4096 && head_dim % 4 == 0 && nsplit >= 2 && nsplit <= kPartsMaxSplit;
 }
 
-void launch_linear_mx4_parts(const AttnParts& p, const uint8_t* Q, const uint8_t* SC, int M, int N, int K,
-                             const Epi& ep, hipStream_t s) {
-  Epi e = ep;
-  e.col_scale = nullptr;
-  if (M <= 1) gemv_mx4_launch<2, 1, false, true>(Q, SC, nullptr, LnArgs{}, M, N, K, e, s, p);
-  else gemv_mx4_launch<2, 2, false, true>(Q, SC, nullptr, LnArgs{}, M, N, K, e, s, p);
+double wmat_stream_bytes(const WMat& w, int N, int K, size_t esz) {
+  if (w.blk_scale) return (double)N * K * 0.53125;
+  if (w.row_scale) return (double)N * K + (double)N * 4;
+  return (double)N * K * esz;
 }
 
-void launch_linear_mx4(const void* X, const uint8_t* Q, const uint8_t* SC, void* w_scratch, int M, int N, int K,
-                       const Epi& ep, hipStream_t s) {
+void launch_wmat(int is_bf16, const void* X, const WMat& w, void* w_scratch, int M, int N, int K, const Epi& ep,
+                 hipStream_t s) {
+  if (!wmat_quantised(w)) {
+    launch_linear(is_bf16, X, w.w, M, N, K, ep, s);
+    return;
+  }
   if (M <= 0) return;
   if (ep.kind == EPI_ARGMAX) abort();  // the tied lm_head stays bf16
   const bf16* x = (const bf16*)X;
   Epi e = ep;
-  e.col_scale = nullptr;
-  if (linear_mx4_gemv(M, N, K)) {
-    const LnArgs ln{};
-    if (M <= 1) gemv_mx4_launch<2, 1>(Q, SC, x, ln, M, N, K, e, s);
-    else if (M <= 2) gemv_mx4_launch<2, 2>(Q, SC, x, ln, M, N, K, e, s);
-    else if (M <= 4) gemv_mx4_launch<2, 4>(Q, SC, x, ln, M, N, K, e, s);
-    else gemv_mx4_launch<1, 8>(Q, SC, x, ln, M, N, K, e, s);
+  e.col_scale = w.row_scale;
+  // int8, batched decode (4 < M <= 32): the int8 gemv_ldsw4 / tile GEMV converts in registers (no dequant pass);
+  // at M = 8 it reads the weights once where gemv_q8 re-reads activations per row (bloom-7b1 int8 B=8)
+  if (w.row_scale && M > 4 && M <= 32 && gemv_tiles_dispatch<int8_t>(x, (const int8_t*)w.w, M, N, K, e, s)) return;
+  if (w.blk_scale ? linear_mx4_gemv(M, N, K) : linear_q8_gemv(M, K)) {
+    gemv_wq_launch<false, false>(w, x, LnArgs{}, AttnParts{}, M, N, K, e, s);
     return;
   }
-  // prefill and batches: exact bf16 weights in the scratch, then the bf16 stage's own GEMM / batched GEMV
-  launch_dequant_mx4(Q, SC, w_scratch, N, K, s);
+  // prefill and batches: the weights to the bf16 scratch (MXFP4: exact; int8: Q, the epilogue applies the row scale),
+  // then the bf16 stage's own GEMM / batched GEMV
+  if (w.blk_scale) launch_dequant_mx4((const uint8_t*)w.w, w.blk_scale, w_scratch, N, K, s);
+  else launch_dequant_rows((const int8_t*)w.w, nullptr, w_scratch, N, K, s);
   launch_linear(1, X, w_scratch, M, N, K, e, s);
+}
+
+void launch_wmat_ln(int is_bf16, const float* x, int row_stride, int row_offset, const void* gamma, const void* beta,
+                    float eps, void* xn_scratch, const WMat& w, int M, int N, int K, const Epi& ep, hipStream_t s) {
+  if (!wmat_quantised(w)) {
+    launch_linear_ln(is_bf16, x, row_stride, row_offset, gamma, beta, eps, xn_scratch, w.w, M, N, K, ep, s);
+    return;
+  }
+  const LnArgs ln{x, row_stride, row_offset, (const bf16*)gamma, (const bf16*)beta, eps};
+  gemv_wq_launch<true, false>(w, nullptr, ln, AttnParts{}, M, N, K, ep, s);
+}
+
+void launch_wmat_parts(const AttnParts& p, const WMat& w, int M, int N, int K, const Epi& ep, hipStream_t s) {
+  if (!wmat_quantised(w)) launch_linear_parts(p, w.w, M, N, K, ep, s);
+  else gemv_wq_launch<false, true>(w, nullptr, LnArgs{}, p, M, N, K, ep, s);
 }
 
 // ------------------------------------------------------------------------------------

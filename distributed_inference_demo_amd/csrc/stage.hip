@@ -1141,9 +1141,13 @@ struct ProfScope {
 };
 }  // namespace
 
-// Algorithmic bytes of one weight GEMV launch (decode): weights + bias + activations in/out.
-static double gemv_bytes(const bs_stage* s, int M, int N, int K, int out_bytes) {
-  return (double)N * K * s->esz + (double)N * s->esz + (double)M * K * s->esz + (double)M * N * out_bytes;
+// Matrix t of a block as the kernels take it: the one place of the forward that knows the weight formats
+// (int8 with row scales, MXFP4 with block scales, else the stage's own type).
+static WMat wmat(const Layer& w, int t) { return WMat{w.t[t], w.sc[t], w.mxs[t]}; }
+
+// Algorithmic bytes of one weight GEMV launch (decode): weights (+ scales) + bias + activations in/out.
+static double gemv_bytes(const bs_stage* s, const WMat& w, int M, int N, int K, int out_bytes) {
+  return wmat_stream_bytes(w, N, K, s->esz) + (double)N * s->esz + (double)M * K * s->esz + (double)M * N * out_bytes;
 }
 
 // The forward's GEMVs may split K through the stage's workspace (see kSkCap).
@@ -1153,83 +1157,24 @@ static Epi with_splitk(const bs_stage* s, const Epi& ep) {
   return e;
 }
 
-static void linear(bs_stage* s, hipStream_t st, const void* X, const void* W, int M, int N, int K, const Epi& ep,
+// One profile record per launch: a weight-stream-bound GEMV by its bytes (class 1), a GEMM by its flops (class 2).
+static void linear(bs_stage* s, hipStream_t st, const void* X, const WMat& w, int M, int N, int K, const Epi& ep,
                    int out_bytes) {
-  const bool decode = M <= 32 && s->bf16;
-  if (decode) {
-    ProfScope p(s, st, 1, gemv_bytes(s, M, N, K, out_bytes));
-    launch_linear(s->bf16, X, W, M, N, K, ep, st);
-  } else {
-    ProfScope p(s, st, 2, 2.0 * M * N * K);
-    launch_linear(s->bf16, X, W, M, N, K, ep, st);
-  }
+  const bool gemv = wmat_streams(s->bf16, w, M, N, K);
+  ProfScope p(s, st, gemv ? 1 : 2, gemv ? gemv_bytes(s, w, M, N, K, out_bytes) : 2.0 * M * N * K);
+  launch_wmat(s->bf16, X, w, s->wtmp, M, N, K, ep, st);
 }
 
 static void linear_ln(bs_stage* s, hipStream_t st, const float* x, int row_stride, int row_offset, const void* g,
-                      const void* b, const void* W, int M, int N, int K, const Epi& ep, int out_bytes) {
-  const bool decode = M <= 32 && s->bf16;
-  if (decode) {
-    ProfScope p(s, st, 1, gemv_bytes(s, M, N, K, out_bytes));
-    launch_linear_ln(s->bf16, x, row_stride, row_offset, g, b, s->d.ln_eps, s->xn, W, M, N, K, ep, st);
-  } else {
-    ProfScope p(s, st, 2, 2.0 * M * N * K);
-    launch_linear_ln(s->bf16, x, row_stride, row_offset, g, b, s->d.ln_eps, s->xn, W, M, N, K, ep, st);
-  }
-}
-
-// Algorithmic bytes of one int8 weight GEMV launch: int8 weights + row scales + bias + activations.
-static double gemv_bytes_q8(const bs_stage* s, int M, int N, int K, int out_bytes) {
-  return (double)N * K + (double)N * 4 + (double)N * s->esz + (double)M * K * s->esz + (double)M * N * out_bytes;
-}
-
-// Algorithmic bytes of one MXFP4 weight GEMV launch: codes and block scales (0.53125 B per weight) + bias +
-// activations.
-static double gemv_bytes_mx4(const bs_stage* s, int M, int N, int K, int out_bytes) {
-  return (double)N * K * 0.53125 + (double)N * s->esz + (double)M * K * s->esz + (double)M * N * out_bytes;
-}
-
-// Block matrix t of a layer: int8 stages stream the int8 weights (launch_linear_q8), MXFP4 stages the fp4 codes
-// (launch_linear_mx4).
-static void wlinear(bs_stage* s, hipStream_t st, const void* X, const Layer& w, int t, int M, int N, int K,
-                    const Epi& ep, int out_bytes) {
-  if (w.mxs[t]) {
-    const bool gemv = linear_mx4_gemv(M, N, K);
-    ProfScope p(s, st, gemv ? 1 : 2, gemv ? gemv_bytes_mx4(s, M, N, K, out_bytes) : 2.0 * M * N * K);
-    launch_linear_mx4(X, (const uint8_t*)w.t[t], w.mxs[t], s->wtmp, M, N, K, ep, st);
-  } else if (!w.sc[t]) {
-    linear(s, st, X, w.t[t], M, N, K, ep, out_bytes);
-  } else if (M <= 32) {  // int8 GEMV / batched tile GEMV: weight-stream bound
-    ProfScope p(s, st, 1, gemv_bytes_q8(s, M, N, K, out_bytes));
-    launch_linear_q8(X, (const int8_t*)w.t[t], w.sc[t], s->wtmp, M, N, K, ep, st);
-  } else {
-    ProfScope p(s, st, 2, 2.0 * M * N * K);
-    launch_linear_q8(X, (const int8_t*)w.t[t], w.sc[t], s->wtmp, M, N, K, ep, st);
-  }
-}
-
-static void wlinear_ln(bs_stage* s, hipStream_t st, const float* x, const void* g, const void* b, const Layer& w,
-                       int t, int M, int N, int K, const Epi& ep, int out_bytes) {
-  if (w.mxs[t]) {
-    if (linear_mx4_ln_fused(M, K)) {
-      ProfScope p(s, st, 1, gemv_bytes_mx4(s, M, N, K, out_bytes));
-      launch_linear_mx4_ln(x, 1, 0, g, b, s->d.ln_eps, (const uint8_t*)w.t[t], w.mxs[t], M, N, K, ep, st);
-      return;
-    }
-    launch_ln_rows(x, 1, 0, g, b, s->d.ln_eps, s->xn, M, K, st);
-    wlinear(s, st, s->xn, w, t, M, N, K, ep, out_bytes);
+                      const void* b, const WMat& w, int M, int N, int K, const Epi& ep, int out_bytes) {
+  if (!wmat_takes_ln(w, M, K)) {  // a quantised matrix beyond its LN-fused shapes: LayerNorm on its own, unrecorded
+    launch_ln_rows(x, row_stride, row_offset, g, b, s->d.ln_eps, s->xn, M, K, st);
+    linear(s, st, s->xn, w, M, N, K, ep, out_bytes);
     return;
   }
-  if (!w.sc[t]) {
-    linear_ln(s, st, x, 1, 0, g, b, w.t[t], M, N, K, ep, out_bytes);
-    return;
-  }
-  if (linear_q8_ln_fused(M, K)) {
-    ProfScope p(s, st, 1, gemv_bytes_q8(s, M, N, K, out_bytes));
-    launch_linear_q8_ln(x, 1, 0, g, b, s->d.ln_eps, (const int8_t*)w.t[t], w.sc[t], M, N, K, ep, st);
-    return;
-  }
-  launch_ln_rows(x, 1, 0, g, b, s->d.ln_eps, s->xn, M, K, st);
-  wlinear(s, st, s->xn, w, t, M, N, K, ep, out_bytes);
+  const bool gemv = wmat_streams(s->bf16, w, M, N, K);
+  ProfScope p(s, st, gemv ? 1 : 2, gemv ? gemv_bytes(s, w, M, N, K, out_bytes) : 2.0 * M * N * K);
+  launch_wmat_ln(s->bf16, x, row_stride, row_offset, g, b, s->d.ln_eps, s->xn, w, M, N, K, ep, st);
 }
 
 // Does a forward of B rows take the screened greedy tail (else the full head)?
@@ -1313,12 +1258,13 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     }
     bool done = false;
     if (l == 0 && emb_fused) {
-      ProfScope p(s, st, 1, gemv_bytes(s, M, 3 * h, h, 4) + (double)M * h * (s->esz + 4));
+      ProfScope p(s, st, 1, gemv_bytes(s, wmat(w, T_QKV_W), M, 3 * h, h, 4) + (double)M * h * (s->esz + 4));
       done = launch_linear_emb(ids, s->wemb, s->emb_g, s->emb_b, s->xa, w.t[T_LN1_G], w.t[T_LN1_B], d.ln_eps,
                                w.t[T_QKV_W], M, 3 * h, h, with_splitk(s, e), st);
       if (!done) launch_layernorm(s->bf16, s->wemb, ids, 0, 0, s->emb_g, s->emb_b, s->xa, 1, M, h, d.ln_eps, st);
     }
-    if (!done) wlinear_ln(s, st, cur, w.t[T_LN1_G], w.t[T_LN1_B], w, T_QKV_W, M, 3 * h, h, with_splitk(s, e), 4);
+    if (!done)
+      linear_ln(s, st, cur, 1, 0, w.t[T_LN1_G], w.t[T_LN1_B], wmat(w, T_QKV_W), M, 3 * h, h, with_splitk(s, e), 4);
     // attention
     AttnArgs a{};
     a.q = s->q; a.k_cache = kbase; a.v_cache = kbase + s->kv_half; a.ctx_out = s->ctx; a.slopes = s->slopes;
@@ -1331,10 +1277,8 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     a.pf_past_max = *std::max_element(pasts.begin(), pasts.end());
     // a split decode context merges in the dense GEMV's prologue when that kernel can take it
     const int nsplit = S == 1 ? attention_decode_splits(B, nh, s->max_chunks) : 1;
-    a.defer_merge = s->bf16 && nsplit > 1 &&
-                    (w.mxs[T_DENSE_W] ? linear_mx4_parts_supported(M, h, hd, nsplit)
-                     : w.sc[T_DENSE_W] ? linear_q8_parts_supported(M, h, hd, nsplit)
-                                       : linear_parts_supported(M, h, hd, nsplit));
+    const WMat dense = wmat(w, T_DENSE_W);
+    a.defer_merge = s->bf16 && nsplit > 1 && wmat_parts_supported(dense, M, h, hd, nsplit);
     // a = x + dense(ctx)
     Epi e2{};
     e2.kind = EPI_RESID; e2.bias = w.t[T_DENSE_B]; e2.out_f32 = s->attn; e2.resid = cur; e2.ldo = h;
@@ -1360,24 +1304,21 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     }
     if (a.defer_merge) {
       const AttnParts parts{s->part_acc, s->part_ml, nsplit, nh, hd, s->max_chunks, slot};
-      ProfScope p(s, st, 1, w.mxs[T_DENSE_W] ? gemv_bytes_mx4(s, M, h, h, 4)
-                            : w.sc[T_DENSE_W] ? gemv_bytes_q8(s, M, h, h, 4) : gemv_bytes(s, M, h, h, 4));
-      if (w.mxs[T_DENSE_W])
-        launch_linear_mx4_parts(parts, (const uint8_t*)w.t[T_DENSE_W], w.mxs[T_DENSE_W], M, h, h, e2, st);
-      else if (w.sc[T_DENSE_W]) launch_linear_q8_parts(parts, (const int8_t*)w.t[T_DENSE_W], w.sc[T_DENSE_W], M, h, h, e2, st);
-      else launch_linear_parts(parts, w.t[T_DENSE_W], M, h, h, e2, st);
+      ProfScope p(s, st, 1, gemv_bytes(s, dense, M, h, h, 4));
+      launch_wmat_parts(parts, dense, M, h, h, e2, st);
     } else {
-      wlinear(s, st, s->ctx, w, T_DENSE_W, M, h, h, with_splitk(s, e2), 4);
+      linear(s, st, s->ctx, dense, M, h, h, with_splitk(s, e2), 4);
     }
     // x2 = LN_post(a); g = gelu(x2 W1 + b1)
     Epi e3{};
     e3.kind = EPI_GELU; e3.bias = w.t[T_FC1_B]; e3.out_act = s->g; e3.ldo = 4 * h;
-    wlinear_ln(s, st, s->attn, w.t[T_LN2_G], w.t[T_LN2_B], w, T_FC1_W, M, 4 * h, h, with_splitk(s, e3), (int)s->esz);
+    linear_ln(s, st, s->attn, 1, 0, w.t[T_LN2_G], w.t[T_LN2_B], wmat(w, T_FC1_W), M, 4 * h, h, with_splitk(s, e3),
+              (int)s->esz);
     // x = a + g W2 + b2
     float* nxt = (!d.is_last && !host_io && l == s->L - 1) ? (float*)out : (cur == s->xa ? s->xb : s->xa);
     Epi e4{};
     e4.kind = EPI_RESID; e4.bias = w.t[T_FC2_B]; e4.out_f32 = nxt; e4.resid = s->attn; e4.ldo = h;
-    wlinear(s, st, s->g, w, T_FC2_W, M, h, 4 * h, with_splitk(s, e4), 4);
+    linear(s, st, s->g, wmat(w, T_FC2_W), M, h, 4 * h, with_splitk(s, e4), 4);
     cur = nxt;
   }
 
@@ -1430,7 +1371,7 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
       e.logits = dev_logits;
     }
     int* tok_out = host_io ? s->vf_tok : (int*)out;
-    linear_ln(s, st, cur, 1, 0, s->lnf_g, s->lnf_b, s->wemb, M, V, h, with_splitk(s, e), 0);
+    linear_ln(s, st, cur, 1, 0, s->lnf_g, s->lnf_b, WMat{s->wemb}, M, V, h, with_splitk(s, e), 0);
     launch_argmax_finalize(s->vf_keys, M, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S, B);
     if (host_io) {
       HIP_TRY(hipMemcpyAsync(out, s->vf_tok, (size_t)M * 4, hipMemcpyDeviceToHost, st));
@@ -1462,7 +1403,7 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
       launch_head_pick(s->hs, cur, S, S - 1, s->lnf_g, s->lnf_b, d.ln_eps, s->wemb, B, V, h, e, s->cus, tok_out,
                        s->past_dev, S, st);
     } else {
-      linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, s->wemb, B, V, h, with_splitk(s, e), 0);
+      linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
       // the pick is the step's last kernel: it advances the device copy of every row's past_len by S
       if (sample)
         launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
@@ -1504,7 +1445,7 @@ extern "C" int bs_head_slice(bs_stage* s, const void* xn, int32_t B, const uint6
   const int n = s->hv1 - s->hv0;
   Epi e{};
   e.kind = EPI_ARGMAX; e.keys = s->keys; e.ldo = n; e.col_offset = s->hv0;
-  linear(s, st, xn, s->hw, B, n, s->d.hidden, e, 0);
+  linear(s, st, xn, WMat{s->hw}, B, n, s->d.hidden, e, 0);
   launch_argmax_finalize(s->keys, B, n / 16, (const unsigned long long*)keys_in, (unsigned long long*)keys_out,
                          tokens, st);
   hipError_t err = hipGetLastError();

@@ -78,6 +78,23 @@ def test_int8_family_block_prefill_and_decode(fam):
                 "bf16", f"{fam} int8 S=1 past=22")
 
 
+@pytest.mark.parametrize("fam", ["560m", "1b1"])
+def test_int8_family_width_block_decode_chunks(fam):
+    """One block at h = 1024 and 1536, passes of 15 (prefill), then 1, 2, 3 and 4 rows over the growing cache: every
+    <rows per wave, rows> instance of the int8 GEMV up to 4 rows, LayerNorm-fused.  K = 1536 is the narrowest width
+    at which the int8 row ends inside a 1024-column step (the clamped last load, the skipped step)."""
+    f = load_parts("family_blocks")
+    h, nh, _, V, seed = (int(v) for v in f[fam + "_config"])
+    gs, os_ = pair8(h, nh, 1, V, 0, 1, seed, max_ctx=40, max_tokens=16, is_last=False)
+    ids = gen_np.prompt_ids(7, 1, 25, V).astype(np.int32)
+    past = 0
+    for S in (15, 1, 2, 3, 4):
+        x = ids[:, past:past + S]
+        check_close(gs.forward_host(x, 1, S, past_len=past), os_.forward(x, 1, S, past_len=past), "bf16",
+                    f"{fam} int8 S={S} past={past}")
+        past += S
+
+
 @pytest.mark.parametrize("B", [1, 2, 4, 8, 20])
 def test_int8_batched_greedy_decode(B):
     """Whole model (embedding .. argmax head), B rows at a slot offset: int8 GEMVs for B <= 8, the

@@ -24,20 +24,20 @@ def main():
     cur = None
     rows = []
     for line in notes.splitlines():
-        m = re.match(r"\s+\.(name|vgpr_count|sgpr_count|vgpr_spill_count|private_segment_fixed_size|agpr_count):\s+(\S+)", line)
-        if not m:
-            continue
-        k, v = m.groups()
-        if k == "name":
-            cur = {"name": v}
+        # a kernel's record is a list item at two spaces whose keys come sorted (.agpr_count first, .name in the middle)
+        m = re.match(r"  (- | {2})\.(name|vgpr_count|sgpr_count|vgpr_spill_count|private_segment_fixed_size|agpr_count|"
+                     r"group_segment_fixed_size):\s+(\S+)", line)
+        if line.startswith("  - ."):
+            cur = {}
             rows.append(cur)
-        elif cur is not None:
-            cur[k] = v
+        if m and cur is not None:
+            cur[m.group(2)] = m.group(3)
     for r in rows:
-        if pats and not any(p in r["name"] for p in pats):
+        if "name" not in r or (pats and not any(p in r["name"] for p in pats)):
             continue
         print(f"{r['name'][:90]:90s} vgpr {r.get('vgpr_count', '?'):>4s} agpr {r.get('agpr_count', '?'):>4s} "
-              f"spill {r.get('vgpr_spill_count', '?'):>4s} scratch {r.get('private_segment_fixed_size', '?')}")
+              f"sgpr {r.get('sgpr_count', '?'):>4s} spill {r.get('vgpr_spill_count', '?'):>4s} "
+              f"scratch {r.get('private_segment_fixed_size', '?')} lds {r.get('group_segment_fixed_size', '?')}")
 
 
 if __name__ == "__main__":
