@@ -195,6 +195,42 @@ void launch_topk_sample(const unsigned long long* keys, int ntiles, const float*
                         hipStream_t s, int* past_adv = nullptr);
 void launch_set_past(int* past_dev, const int* values, int n, hipStream_t s);
 
+// ---- Per-row nucleus sampling (include/bloomstage.h "Per-row sampling"; row_sample.hip) ----
+struct RowSamplerDev {  // one entry of the device table [max_batch]
+  int top_k;
+  float top_p;
+  float temperature;
+  int active;           // 0: the row takes the first index of its largest logit
+  uint64_t seed;
+};
+struct RowDrawDev {     // the layout of bs_row_draw
+  float threshold;
+  int n_nucleus, n_candidates;
+  uint32_t u24;
+  uint64_t mass_nucleus, mass_candidates;
+  int token, position;
+};
+struct RsState;
+struct RowSampleBufs {
+  RowSamplerDev* table;        // [max_batch]
+  unsigned long long* rowmax;  // [max_batch] max (key << 32 | ~index) of the step (zero between steps)
+  uint32_t* hcnt;              // [max_batch][6][2048] count histograms of the six digit passes (zero between steps)
+  unsigned long long* hmass;   // [max_batch][3][2048] fixed-point mass histograms of the last three
+  RowDrawDev* draw;            // [max_batch] read-out of each row's last draw
+  RsState* st;                 // [max_batch][6] what one launch hands to the next
+};
+// Bytes of all of the above for max_batch rows; offsets[6] receives where each array starts.  The buffer must be
+// zero before the first launch_row_sample.
+size_t row_sample_bytes(int max_batch, size_t* offsets);
+RowSampleBufs row_sample_bufs(char* base, const size_t* offsets);
+// table[slot .. slot + n) = rows[0..n) (host), stream ordered, by kernel arguments (set_past_kernel's pattern).
+void launch_row_table(const RowSampleBufs& rb, int slot, const RowSamplerDev* rows, int n, hipStream_t s);
+// Sample (or, for rows without state, take the first index of the largest logit of) rows [slot, slot + B) from
+// logits [B][ld], V columns each.  Row b's position is positions[b] (host, passed by value) or, when positions is
+// null, past_dev[b] + seq.  The last launch writes tokens[b], the row's read-out and past_adv[b] += seq (optional).
+void launch_row_sample(const RowSampleBufs& rb, const float* logits, int ld, int V, int slot, int B,
+                       const int* positions, const int* past_dev, int seq, int* tokens, int* past_adv, hipStream_t s);
+
 // ---- Weight-only int8 (bf16 stages with BS_FLAG_INT8_WEIGHTS; kernels.hip "Weight-only int8") ----
 // Q[n][k] = rne(W[n][k] / scale[n]), scale[n] = max_k |W[n][k]| / 127 (1 for a zero row); W bf16 [N][K].
 void launch_quantize_rows(const void* W_bf16, int8_t* Q, float* scale, int N, int K, hipStream_t s);

@@ -66,12 +66,13 @@ static bool is_matrix(int t) { return t == T_QKV_W || t == T_DENSE_W || t == T_F
 
 struct GraphKey {
   int B, seq, slot, flags;
+  int rows;  // the tail runs the per-row sampler (a row of the call holds sampler state)
   const void* in;
   void* out;
   float* logits;
   hipStream_t st;
   bool operator==(const GraphKey& o) const {
-    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && in == o.in && out == o.out && logits == o.logits &&
+    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && rows == o.rows && in == o.in && out == o.out && logits == o.logits &&
            st == o.st;
   }
 };
@@ -202,6 +203,13 @@ struct bs_stage {
   int vf_stride = 0;                   // attention_verify_split_stride
   unsigned long long* vf_keys = nullptr;  // [kVerifyMaxTokens][V/16] (last stage)
   int* vf_tok = nullptr;               // [kVerifyMaxTokens] host-I/O staging of the ids
+  // per-row sampling (row_sample.hip): the device table, histograms and read-outs, one allocation made by the first
+  // bs_set_row_sampler / bs_sample_logits (null: never used); rs_host mirrors the table for routing
+  char* rs_base = nullptr;
+  size_t rs_bytes = 0;                 // rs_base, plus sample_logits when that call allocated it
+  RowSampleBufs rs{};
+  std::vector<RowSamplerDev> rs_host;  // [max_batch]
+  int rs_active = 0;                   // rows that hold state
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -342,6 +350,7 @@ static void free_stage(bs_stage* s) {
   if (s->hs_base) hipFree(s->hs_base);
   if (s->sc_base) hipFree(s->sc_base);
   if (s->vf_base) hipFree(s->vf_base);
+  if (s->rs_base) hipFree(s->rs_base);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
@@ -788,7 +797,7 @@ extern "C" int bs_stage_info(const bs_stage* s, bs_stage_desc* d, uint64_t* wb, 
   if (wb) *wb = s->wbytes;
   if (kvb) *kvb = s->kvbytes;
   // the head-screening shadow copy, the int8 KV staging, the scoring and the verify buffers count as workspace
-  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + s->vf_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
+  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + s->vf_bytes + s->rs_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
   return BS_OK;
 }
 
@@ -1177,10 +1186,18 @@ static void linear_ln(bs_stage* s, hipStream_t st, const float* x, int row_strid
   launch_wmat_ln(s->bf16, x, row_stride, row_offset, g, b, s->d.ln_eps, s->xn, w, M, N, K, ep, st);
 }
 
-// Does a forward of B rows take the screened greedy tail (else the full head)?
-static bool head_screened(const bs_stage* s, int B, bool want_logits) {
+// Does a row of [slot, slot + B) hold sampler state (bs_set_row_sampler)?  Then the tail is the per-row sampler.
+static bool rows_sampled(const bs_stage* s, int slot, int B) {
+  if (!s->rs_active) return false;
+  for (int b = 0; b < B; b++)
+    if (s->rs_host[slot + b].active) return true;
+  return false;
+}
+
+// Does a forward of B rows at `slot` take the screened greedy tail (else the full head)?
+static bool head_screened(const bs_stage* s, int slot, int B, bool want_logits) {
   return s->hs_on && s->hs_base && s->d.is_last && !s->n_labels && s->top_k <= 1 && !want_logits &&
-         head_screen_supported(B, s->d.hidden);
+         head_screen_supported(B, s->d.hidden) && !rows_sampled(s, slot, B);
 }
 
 // Device staging for logits requested with host I/O: one buffer per stage, grown on demand (a
@@ -1380,6 +1397,7 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
   } else if (d.is_last) {
     // ln_f on each row's last position, tied lm_head, token pick (greedy argmax or top-k sample)
     const bool sample = s->top_k > 1;
+    const bool rows = rows_sampled(s, slot, B);  // excludes sample (bs_set_row_sampler / bs_set_sampling)
     Epi e{};
     e.kind = EPI_ARGMAX; e.keys = s->keys; e.logits = want_logits && !host_io ? logits : nullptr; e.ldo = V;
     e.key_hi_index = sample ? 1 : 0;  // sampling ranks equal logits by the higher index (decoding.cpp:44-45)
@@ -1389,9 +1407,9 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
       if (rc != BS_OK) return rc;
       e.logits = dev_logits;
     }
-    if (sample && !e.logits) e.logits = s->sample_logits;
+    if ((sample || rows) && !e.logits) e.logits = s->sample_logits;
     int* tok_out = host_io ? s->tok : (int*)out;
-    const bool screened = head_screened(s, B, want_logits);
+    const bool screened = head_screened(s, slot, B, want_logits);
     if (screened) {
       // greedy, no logits, <= 2 rows: int8 screening pass, then the exact head on the few tiles that can win
       {  // class 1 counts the bytes the screen really streams: int8 rows, scales, bound constants, rows in, hi/lo out
@@ -1405,7 +1423,9 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     } else {
       linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
       // the pick is the step's last kernel: it advances the device copy of every row's past_len by S
-      if (sample)
+      if (rows)  // rows of the call without state get the first index of their largest logit from the same kernels
+        launch_row_sample(s->rs, e.logits, V, V, slot, B, nullptr, past_dev, S, tok_out, s->past_dev, st);
+      else if (sample)
         launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
                            past_dev, S, tok_out, st, s->past_dev);
       else
@@ -1459,6 +1479,7 @@ extern "C" int bs_set_sampling(bs_stage* s, int32_t top_k, float temperature, ui
   if (top_k > 1 && (!s->d.is_last || s->n_labels))
     return fail(BS_ERR_UNSUPPORTED, "sampling needs the last stage of a generation model (whole lm_head)");
   if (top_k > 1 && !(temperature > 0.f)) return fail(BS_ERR_INVALID, "temperature must be positive");
+  if (top_k > 1 && s->rs_active) return fail(BS_ERR_STATE, "rows hold per-row sampler state (bs_set_row_sampler)");
   HIP_TRY(hipSetDevice(s->d.device));
   if (top_k > 1 && !s->sample_logits) {
     HIP_TRY(hipStreamSynchronize(s->own));
@@ -1472,6 +1493,117 @@ extern "C" int bs_set_sampling(bs_stage* s, int32_t top_k, float temperature, ui
   HIP_TRY(hipDeviceSynchronize());
   for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
   s->graphs.clear();
+  return BS_OK;
+}
+
+// ---- per-row sampling (row_sample.hip)
+static_assert(sizeof(bs_row_draw) == sizeof(RowDrawDev) && sizeof(bs_row_draw) == 40, "bs_row_draw layout");
+
+// The table, histograms and read-outs, and the [max_batch][V] logits buffer if bs_set_sampling has not made it.
+static int row_sampler_buffers(bs_stage* s) {
+  if (s->rs_base) return BS_OK;
+  size_t off[6];
+  const size_t bytes = row_sample_bytes(s->d.max_batch, off);
+  char* base = nullptr;
+  if (hipMalloc((void**)&base, bytes) != hipSuccess)
+    return fail(BS_ERR_OOM, "row sampler buffers allocation failed (" + std::to_string(bytes) + " B)");
+  // zeroed before any stream can write the table (a plain hipMemset of device memory may still be running when it
+  // returns, and the caller's stream is not ordered behind it)
+  if (hipMemsetAsync(base, 0, bytes, s->own) != hipSuccess || hipStreamSynchronize(s->own) != hipSuccess) {
+    hipFree(base);
+    return fail(BS_ERR_DEVICE, "row sampler buffers memset");
+  }
+  size_t lb = 0;
+  if (!s->sample_logits) {
+    lb = (size_t)s->d.max_batch * s->d.vocab * 4;
+    if (hipMalloc((void**)&s->sample_logits, lb) != hipSuccess) {
+      s->sample_logits = nullptr;
+      hipFree(base);
+      return fail(BS_ERR_OOM, "sampling logits allocation failed");
+    }
+  }
+  s->rs_base = base;
+  s->rs_bytes = bytes + lb;
+  s->rs = row_sample_bufs(base, off);
+  s->rs_host.assign(s->d.max_batch, RowSamplerDev{});
+  return BS_OK;
+}
+
+static int row_sampler_stage_check(const bs_stage* s) {
+  if (s->n_labels || !s->d.is_last || !s->wemb || s->hv0 != 0 || s->hv1 != s->d.vocab)
+    return fail(BS_ERR_UNSUPPORTED, "per-row sampling needs the last stage of a generation model (whole lm_head)");
+  return BS_OK;
+}
+
+extern "C" int bs_set_row_sampler(bs_stage* s, int32_t slot, int32_t count, const bs_row_sampler* params, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  int rc = row_sampler_stage_check(s);
+  if (rc) return rc;
+  if (count <= 0 || slot < 0 || slot > s->d.max_batch - count) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (params && s->top_k > 1) return fail(BS_ERR_STATE, "bs_set_sampling holds top_k > 1");
+  std::vector<RowSamplerDev> rows(count, RowSamplerDev{});
+  for (int i = 0; params && i < count; i++) {
+    const bs_row_sampler& p = params[i];
+    if (p.top_k < 0) return fail(BS_ERR_INVALID, "top_k must be >= 0");
+    if (!(p.top_p > 0.f && p.top_p <= 1.f)) return fail(BS_ERR_INVALID, "top_p must be in (0, 1]");
+    if (!(p.temperature > 0.f) || std::isinf(p.temperature)) return fail(BS_ERR_INVALID, "temperature must be positive and finite");
+    rows[i] = RowSamplerDev{p.top_k, p.top_p, p.temperature, 1, p.seed};
+  }
+  if (!params && !s->rs_base) return BS_OK;  // nothing was ever set
+  HIP_TRY(hipSetDevice(s->d.device));
+  if ((rc = row_sampler_buffers(s)) != BS_OK) return rc;
+  launch_row_table(s->rs, slot, rows.data(), count, stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("row sampler table: ") + hipGetErrorString(err));
+  for (int i = 0; i < count; i++) {
+    s->rs_active += rows[i].active - s->rs_host[slot + i].active;
+    s->rs_host[slot + i] = rows[i];
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_sample_logits(bs_stage* s, int32_t slot, int32_t batch, const int32_t* positions, const float* logits,
+                                int32_t ld, int32_t* tokens, int32_t flags, void* stream) {
+  if (!s || !positions || !logits || !tokens) return fail(BS_ERR_INVALID, "stage/positions/logits/tokens is NULL");
+  int rc = row_sampler_stage_check(s);
+  if (rc) return rc;
+  const int V = s->d.vocab;
+  if (batch <= 0 || slot < 0 || slot > s->d.max_batch - batch) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (ld < V) return fail(BS_ERR_INVALID, "ld must be >= vocab");
+  if (flags & ~BS_STEP_HOST_IO) return fail(BS_ERR_INVALID, "only BS_STEP_HOST_IO is valid here");
+  for (int b = 0; b < batch; b++)
+    if (positions[b] < 0) return fail(BS_ERR_INVALID, "positions must be >= 0");
+  HIP_TRY(hipSetDevice(s->d.device));
+  if ((rc = row_sampler_buffers(s)) != BS_OK) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  const bool host_io = (flags & BS_STEP_HOST_IO) != 0;
+  const float* dl = logits;
+  int* dt = tokens;
+  if (host_io) {
+    float* stage_l = nullptr;
+    const size_t n = (size_t)(batch - 1) * ld + V;  // the last row may end at its V-th column
+    if ((rc = logits_staging(s, ((size_t)batch * ld) * 4, st, &stage_l)) != BS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(stage_l, logits, n * 4, hipMemcpyHostToDevice, st));
+    dl = stage_l;
+    dt = s->tok;
+  }
+  launch_row_sample(s->rs, dl, ld, V, slot, batch, positions, nullptr, 0, dt, nullptr, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("row sampler: ") + hipGetErrorString(err));
+  if (host_io) {
+    HIP_TRY(hipMemcpyAsync(tokens, s->tok, (size_t)batch * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_read_row_draw(bs_stage* s, int32_t slot, bs_row_draw* out) {
+  if (!s || !out) return fail(BS_ERR_INVALID, "stage/out is NULL");
+  if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot out of range");
+  if (!s->rs_base) return fail(BS_ERR_STATE, "the stage never ran the per-row sampler");
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, s->rs.draw + slot, sizeof(*out), hipMemcpyDeviceToHost));
   return BS_OK;
 }
 
@@ -1545,6 +1677,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     if (s->top_k > 1) return fail(BS_ERR_STATE, "BS_STEP_VERIFY needs the greedy pick (bs_set_sampling top_k <= 1)");
     if (d.is_last && (!s->wemb || s->hv0 != 0 || s->hv1 != d.vocab))
       return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a last stage needs the whole lm_head");
+    if (rows_sampled(s, slot, B)) return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a row that holds sampler state");
   }
   if (!in || (!out && !sc)) return fail(BS_ERR_INVALID, "in/out is NULL");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
@@ -1587,7 +1720,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   s->past_next_valid = false;  // until this forward is enqueued
   const bool graph = (S == 1 || verify) && !host_io && s->prof.cls == 0 && s->graphs_on && !sc;  // scoring is always eager
   if (graph) {
-    GraphKey key{B, S, slot, step->flags, in, out, logits, st};
+    GraphKey key{B, S, slot, step->flags, rows_sampled(s, slot, B) ? 1 : 0, in, out, logits, st};
     hipGraphExec_t exec = nullptr;
     for (auto& g : s->graphs)
       if (g.first == key) { exec = g.second; break; }
@@ -1631,7 +1764,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   BS_TRACE("hipGetLastError");
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
-  s->hs_last_rows = !sc && !verify && head_screened(s, B, want_logits) ? B : 0;
+  s->hs_last_rows = !sc && !verify && head_screened(s, slot, B, want_logits) ? B : 0;
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)
     s->past_next.assign(pasts.begin(), pasts.end());
     for (int& p : s->past_next) p += S;

@@ -86,6 +86,20 @@ class StageExecutor:
         self._run(lambda h: self.stage.score(inp, targets, top_ids, scores, batch, seq, slot=slot, past_len=past_len,
                                              stream=h), (inp, targets, top_ids, scores))
 
+    def set_row_sampler(self, slot, count=1, **state):
+        """Stage.set_row_sampler (state given) or clear_row_sampler (no state) of KV rows [slot, slot + count),
+        ordered like forward."""
+        def call(h):
+            if state:
+                self.stage.set_row_sampler(slot, count=count, stream=h, **state)
+            else:
+                self.stage.clear_row_sampler(slot, count, stream=h)
+        sh = self._sh if self._sh is not None else torch.cuda.current_stream().cuda_stream
+        if sh:
+            call(sh)
+            return
+        self._run(call, ())
+
     def head_norm(self, hidden, batch, seq, xn):
         sh = torch.cuda.current_stream().cuda_stream
         if sh:
@@ -340,6 +354,15 @@ class Pipeline:
             _recv(tok, self.closer if self.head_split else self.world - 1, self.pf_group)
         return tok
 
+    def set_row_sampler(self, mb, row, **state):
+        """Per-row sampling (bs_set_row_sampler): give row `row` of micro-batch `mb` the sampler state
+        top_k / top_p / temperature / seed, or clear it when no state is given.  Acts on the last rank, which holds
+        the whole lm_head (build_rank(..., sample=True)), ordered with its forwards; a no-op elsewhere."""
+        if self.is_last:
+            if self.head_split:
+                raise ValueError("per-row sampling needs the whole lm_head on the last stage: build_rank(sample=True)")
+            self.ex.set_row_sampler(mb * self.mb + row, **state)
+
     def finish(self, record=None):
         """Rank 0 collects the tokens of the last round; everyone drains its sends.  Later steps
         continue from those tokens."""
@@ -514,11 +537,19 @@ def connect_p2p(rank, world, head_split, groups, device):
 
 
 def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb_rows=1, n_mb=None, max_ctx=1024,
-               max_seq=512, seed=0, head_split=None, executor_factory=None, n_labels=0, kv_int8=False):
+               max_seq=512, seed=0, head_split=None, executor_factory=None, n_labels=0, kv_int8=False, sample=False):
     """Create this rank's stage (server.py:893-905 layer range, plus a vocabulary slice of the
     tied lm_head when head_split) and its Pipeline.  n_labels > 0: the last stage is a sequence-classification
     tail (BS_FLAG_CLASSIFIER; `classify` runs the task) and there is no head ring.  kv_int8: every stage keeps an
-    int8 KV cache (BS_FLAG_INT8_KV; bf16 stages of the HIP library only).  Collective: every rank must call it."""
+    int8 KV cache (BS_FLAG_INT8_KV; bf16 stages of the HIP library only).  sample: the run samples per row
+    (Pipeline.set_row_sampler), which needs the whole lm_head on the last stage, as `score` does: no head ring.
+    Collective: every rank must call it."""
+    if sample:
+        if n_labels:
+            raise ValueError("a classifier tail does not sample")
+        if executor_factory is not None:
+            raise ValueError("per-row sampling is the HIP stage's: not available with an executor_factory")
+        head_split = False
     if n_labels and head_split:
         raise ValueError("a classifier tail holds its own score head: no vocabulary-parallel head ring")
     head_split = (world > 1 and not n_labels) if head_split is None else (head_split and world > 1)

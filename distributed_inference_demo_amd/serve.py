@@ -36,8 +36,14 @@ same vocabulary, e.g. the target's "-int8" variant) proposes up to K tokens a ro
 the target emits the agreeing prefix plus one token.  The tokens are plain greedy decoding's; rank 0 also returns
 the acceptance statistics.  One stage only: the ranks of a pipeline derive their schedule from the prompt lengths
 alone, and how many tokens a pass accepts depends on the data.
+--sample is per-row nucleus sampling (bs_set_row_sampler; the reference's tail draws an unseeded top-k sample,
+decoding.cpp:24-66): the last rank gives the row a sample is admitted into the state (--top-k, --top-p, --temperature,
+request_seed(--sample-seed, sample id)) just before the sample's prefill pass, so its first generated token is already
+sampled.  A draw depends on (seed, position, logits) only, never on the row.  The whole lm_head stays on the last
+stage (no head ring).
 Differences from the reference, by design: full-context decode (the reference
-header feeds only the last token), argmax instead of unseeded top-k, token ids in (no tokenizer).
+header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
+unseeded top-k, token ids in (no tokenizer).
 
   python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 \\
       -m distributed_inference_demo_amd.serve --model bloom-560m --num-sample 8 --max-length 40 \\
@@ -57,6 +63,7 @@ from . import config
 from .pipeline import build_rank, init_distributed
 
 STATES = ("Ready", "Running", "Finish", "Close")  # Client.java status strings, in order
+M64 = (1 << 64) - 1
 
 
 @dataclasses.dataclass
@@ -76,6 +83,11 @@ class RunConfig:
     score: bool = False           # the scoring task: each prompt's log-likelihood and perplexity, one pass a sample
     speculate: int = 0            # speculative decoding: tokens drafted per verify pass (0 = off; one GPU only)
     draft: str = "ngram"          # the drafter: "ngram" (prompt lookup) or a draft model's name (same vocabulary)
+    sample: bool = False          # per-row nucleus sampling instead of greedy decoding (whole lm_head on the last stage)
+    top_k: int = 0                # sampling: keep the top_k largest logits (ties at the k-th kept); 0 = no limit
+    top_p: float = 1.0            # sampling: the nucleus' share of the candidates' mass, in (0, 1]
+    temperature: float = 1.0      # sampling: > 0
+    sample_seed: int = 0          # sampling: sample i draws with request_seed(sample_seed, i)
 
     def __post_init__(self):
         if self.kv not in ("bf16", "int8"):
@@ -89,6 +101,26 @@ class RunConfig:
                 raise ValueError("speculative decoding is a generation task: max_length must be > 0")
             if self.score:
                 raise ValueError("speculative decoding and the scoring task exclude each other")
+        if self.sample:
+            if self.speculate or self.score or self.max_length <= 0:
+                raise ValueError("sample is plain generation: it excludes speculate, score and max_length == 0")
+            if not self.prefill:
+                raise ValueError("sample needs prefill: a row's sampler is set at admission, before its prefill pass")
+            if self.top_k < 0 or not 0.0 < self.top_p <= 1.0 or not 0.0 < self.temperature < float("inf"):
+                raise ValueError("sampling needs top_k >= 0, top_p in (0, 1] and a positive finite temperature "
+                                 f"(got {self.top_k}, {self.top_p}, {self.temperature})")
+            self.head_split = False
+
+
+def request_seed(sample_seed, i):
+    """The seed of sample i's draws: a 64-bit splitmix64 mix of (sample_seed, i), so neighbouring sample ids and
+    neighbouring base seeds give unrelated streams.  Stable: part of a run's reproducibility."""
+    def mix(x):
+        x = (x + 0x9E3779B97F4A7C15) & M64
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
+        return x ^ (x >> 31)
+    return mix((int(sample_seed) & M64) ^ mix((int(i) + 1) & M64))
 
 
 def synthetic_prompts(cfg: RunConfig, vocab):
@@ -125,6 +157,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     if cfg.speculate and world != 1:
         raise ValueError("speculative decoding runs on one stage (world == 1): acceptance is data-dependent, the "
                          "pipeline's schedule is not")
+    if cfg.sample and executor_factory is not None:
+        raise ValueError("sample is the HIP stage's per-row sampler: not available with an executor_factory")
     if cfg.num_sample < 1 or cfg.max_length < 0 or cfg.core_pool_size < 1:
         raise ValueError("num_sample and core_pool_size must be >= 1, max_length >= 0 (0: classification)")
     model = config.get(cfg.model) if isinstance(cfg.model, str) else cfg.model
@@ -182,9 +216,10 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + cfg.max_length + 1, max_seq=max_seq, seed=cfg.seed,
                                 head_split=cfg.head_split, executor_factory=executor_factory,
-                                kv_int8=cfg.kv == "int8")
+                                kv_int8=cfg.kv == "int8", sample=cfg.sample)
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "rounds": T, "prefill": pf})
+    sampling = ({"top_k": cfg.top_k, "top_p": cfg.top_p, "temperature": cfg.temperature} if cfg.sample else None)
     cuda = device.type == "cuda"
     if cuda:
         torch.cuda.set_stream(torch.cuda.Stream(device))  # decode steps are captured as hipGraphs
@@ -204,6 +239,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     t_start = time.perf_counter()
     for t in range(T + 1):
         for i, r in admit[t] if pf else ():
+            if sampling:  # the row's sampler for this request, ordered before its prefill pass (last rank)
+                pipe.set_row_sampler(r // mb, r % mb, seed=request_seed(cfg.sample_seed, i), **sampling)
             tok = pipe.prefill_row(r // mb, r % mb, pids[i] if pids is not None else None, lens[i])
             if rank == 0:
                 first[i] = tok.clone()
@@ -234,6 +271,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     res = {"samples": out, "num_sample": cfg.num_sample, "max_length": cfg.max_length,
            "core_pool_size": cfg.core_pool_size, "stages": world, "prompt_lens": lens, "rounds": T,
            "prefill": pf, "seconds": dt, "tokens_per_s": cfg.num_sample * cfg.max_length / dt}
+    if sampling:
+        res.update(sample=True, sample_seed=cfg.sample_seed, **sampling)
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
     say(STATES[3], {})
     return res

@@ -77,6 +77,19 @@ class Step(ctypes.Structure):
                 ("past_lens", ctypes.POINTER(ctypes.c_int32))]
 
 
+class RowSampler(ctypes.Structure):
+    """bs_row_sampler: the sampler state of one KV row."""
+    _fields_ = [("top_k", ctypes.c_int32), ("top_p", ctypes.c_float), ("temperature", ctypes.c_float),
+                ("seed", ctypes.c_uint64)]
+
+
+class RowDraw(ctypes.Structure):
+    """bs_row_draw: read-out of a row's last draw."""
+    _fields_ = [("threshold", ctypes.c_float), ("n_nucleus", ctypes.c_int32), ("n_candidates", ctypes.c_int32),
+                ("u24", ctypes.c_uint32), ("mass_nucleus", ctypes.c_uint64), ("mass_candidates", ctypes.c_uint64),
+                ("token", ctypes.c_int32), ("position", ctypes.c_int32)]
+
+
 class TensorView(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("ndim", ctypes.c_int32), ("dims", ctypes.c_int64 * 8),
                 ("data", ctypes.c_void_p)]
@@ -89,7 +102,7 @@ EXPORTS = [
     "bs_prompt_ids", "bs_read_weights", "bs_head_norm", "bs_head_slice", "bs_stream_delay", "bs_set_sampling",
     "bs_build_id", "bs_hbm_probe", "bs_mfma_probe", "bs_init_stage_file", "bs_weights_file_probe",
     "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
-    "bs_forward_score",
+    "bs_forward_score", "bs_set_row_sampler", "bs_sample_logits", "bs_read_row_draw",
 ]
 
 _LIB = None
@@ -143,6 +156,9 @@ def lib():
         L.bs_head_norm.argtypes = [vp, vp, i32, i32, vp, vp]
         L.bs_head_slice.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         L.bs_set_sampling.argtypes = [vp, i32, ctypes.c_float, ctypes.c_uint64]
+        L.bs_set_row_sampler.argtypes = [vp, i32, i32, ctypes.POINTER(RowSampler), vp]
+        L.bs_sample_logits.argtypes = [vp, i32, i32, ctypes.POINTER(i32), vp, i32, vp, i32, vp]
+        L.bs_read_row_draw.argtypes = [vp, i32, ctypes.POINTER(RowDraw)]
         L.bs_set_graphs.argtypes = [vp, i32]
         L.bs_set_head_screen.argtypes = [vp, i32]
         L.bs_read_head_screen.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(i32)]
@@ -322,6 +338,51 @@ class Stage:
         """Tail token pick (bs_set_sampling): greedy for top_k <= 1, else seeded top-k sampling in
         decoding.cpp:24-66's order (last stage only)."""
         _check(lib().bs_set_sampling(self._h, int(top_k), float(temperature), int(seed)))
+
+    # ---- per-row sampling (bs_set_row_sampler; last stage of a generation model)
+    def set_row_sampler(self, slot, top_k=0, top_p=1.0, temperature=1.0, seed=0, count=1, stream=None):
+        """Give KV rows [slot, slot + count) a sampler state: top-k (0 = none) / top-p / temperature and the seed of
+        the draws, keyed by (seed, position) only.  Every parameter is one value for all the rows or a sequence of
+        `count` values.  Stream ordered; captured decode graphs stay."""
+        def per_row(v):
+            vs = list(v) if np.ndim(v) else [v] * count
+            if len(vs) != count:
+                raise BloomStageError(f"{len(vs)} sampler values for {count} rows")
+            return vs
+        ks, ps, ts, ss = per_row(top_k), per_row(top_p), per_row(temperature), per_row(seed)
+        arr = (RowSampler * count)(*[RowSampler(int(ks[i]), float(ps[i]), float(ts[i]), int(ss[i]) & (2**64 - 1))
+                                     for i in range(count)])
+        _check(lib().bs_set_row_sampler(self._h, int(slot), int(count), arr, stream))
+
+    def clear_row_sampler(self, slot=None, count=1, stream=None):
+        """Back to greedy for rows [slot, slot + count), or for every row when slot is None."""
+        if slot is None:
+            slot, count = 0, self.max_batch
+        _check(lib().bs_set_row_sampler(self._h, int(slot), int(count), None, stream))
+
+    def sample_logits(self, logits, positions, slot=0, tokens=None, ld=None, stream=None):
+        """bs_sample_logits: run the tail's row sampler on given logits for rows [slot, slot + batch) at
+        `positions` (one int per row).  logits: a numpy array [batch][ld] (host I/O; returns the tokens as int32
+        [batch]) or a device pointer / torch tensor with `tokens` a device buffer of batch int32 (stream ordered)."""
+        pos = [int(p) for p in np.atleast_1d(positions)]
+        batch = len(pos)
+        parr = (ctypes.c_int32 * batch)(*pos)
+        if isinstance(logits, np.ndarray):
+            lg = np.ascontiguousarray(logits, dtype=np.float32).reshape(batch, -1)
+            out = np.empty(batch, np.int32)
+            _check(lib().bs_sample_logits(self._h, int(slot), batch, parr, lg.ctypes.data, lg.shape[1],
+                                          out.ctypes.data, BS_STEP_HOST_IO, stream))
+            return out
+        _check(lib().bs_sample_logits(self._h, int(slot), batch, parr, _ptr(logits), int(ld or self.vocab),
+                                      _ptr(tokens), 0, stream))
+        return tokens
+
+    def read_row_draw(self, slot):
+        """bs_read_row_draw: {"threshold", "n_nucleus", "n_candidates", "u24", "mass_nucleus", "mass_candidates"
+        (2^40 fixed point), "token", "position"} of row `slot`'s last draw.  Synchronises."""
+        d = RowDraw()
+        _check(lib().bs_read_row_draw(self._h, int(slot), ctypes.byref(d)))
+        return {name: getattr(d, name) for name, _ in RowDraw._fields_}
 
     def set_graphs(self, on=True):
         """bs_set_graphs: replay captured decode graphs (default) or launch every step eagerly."""

@@ -264,6 +264,70 @@ int bs_head_slice(bs_stage *stage, const void *xn, int32_t batch, const uint64_t
  *   base_seed ^ request_id, set before the request's first sampled step). */
 int bs_set_sampling(bs_stage *stage, int32_t top_k, float temperature, uint64_t seed);
 
+/* ---- Per-row sampling: top-k / top-p (nucleus) / temperature per KV row ----
+ * Every KV row may hold a sampler state {top_k, top_p, temperature, seed}; a row without one is greedy.  Setting or
+ * clearing a row's state is stream-ordered, does not synchronise and keeps every captured decode graph: a server
+ * sets it when it admits a request into the row.
+ *
+ * Rule, for a row with state, on its fp32 logits l[0..V) (the values BS_STEP_LOGITS returns; all finite):
+ *   weights     w_v = exp((l_v - max l) / temperature).
+ *   candidates  C = the whole vocabulary for top_k == 0 or top_k >= V; else {v : l_v >= the top_k-th largest logit
+ *               value} -- a tie at the k-th value keeps the whole level.
+ *   nucleus     N = {v : l_v >= t}, t = the largest logit value with mass{v in C : l_v >= t} >= top_p * mass(C):
+ *               whole level sets, never a partial tie; top_p == 1 gives N = C; N always holds the top level.
+ *   draw        u = u24 / 2^24, u24 = the top 24 bits of the repo's counter generator (DESIGN.md "Synthetic
+ *               weights": bits(key, i) with key = sm64(seed ^ sm64(0x524F575300000000)), i = position), position =
+ *               the index of the token being generated (past_b + seq).  The KV row is not in the key: a request
+ *               draws the same tokens in whichever row it lands.
+ *   pick        the first v in vocabulary index order, among the members of N, whose running mass exceeds
+ *               u * mass(N).
+ * Arithmetic: masses are 64-bit fixed point, q_v = rint(w_v * 2^40) with w_v from an IEEE fp32 subtraction and
+ * division and expf (one ulp); sums of V <= 2^18 terms stay below 2^58.  -0.0 and +0.0 are one level.  Every
+ * comparison is exact integer arithmetic: mass >= ceil(top_p * mass(C)) with top_p's exact binary value (128-bit
+ * product), running mass > (u24 * mass(N)) >> 24.  Integer sums do not depend on their order, so given the logits a
+ * draw is bit-identical from run to run, between graph replay and eager launch, and independent of the row index,
+ * the batch and the grid; there are no floating-point atomics.  Against the rule evaluated in real arithmetic the
+ * masses are within a relative 2^-17 (argument rounding |arg| * 2^-23 for |arg| <= 40, one ulp of expf) plus V *
+ * 2^-41 of quantisation. */
+typedef struct bs_row_sampler {
+  int32_t top_k;      /* 0 = no top-k limit */
+  float top_p;        /* (0, 1] */
+  float temperature;  /* > 0 */
+  uint64_t seed;
+} bs_row_sampler;
+/* Read-out of a row's last draw.  A row without state: threshold = its largest logit, token = the first index of
+ * it, position as given, the other fields 0. */
+typedef struct bs_row_draw {
+  float threshold;           /* t */
+  int32_t n_nucleus;         /* |N| */
+  int32_t n_candidates;      /* |C| */
+  uint32_t u24;
+  uint64_t mass_nucleus;     /* sum of q_v over N (2^40 fixed point) */
+  uint64_t mass_candidates;  /* sum of q_v over C */
+  int32_t token;
+  int32_t position;
+} bs_row_draw;
+/* Set (params != NULL: [count] states) or clear (params == NULL) the sampler of KV rows [slot, slot + count), ordered
+ * on `stream` (NULL = the stage's own) like a forward.  A bs_forward on a last stage whose rows include at least one
+ * row with state takes the full head (never the int8 screen) and ends in the row sampler, for seq > 1 too (a
+ * prefill's first generated token is sampled); rows of that call without state get the first index of their largest
+ * logit.  A call with no such row is what it was before.  bs_forward_score is unaffected.
+ * BS_ERR_INVALID: top_k < 0, top_p outside (0, 1], temperature <= 0, infinite or NaN, a bad row range.
+ * BS_ERR_UNSUPPORTED: a classifier, a non-last stage, or a stage without the whole lm_head.  BS_ERR_STATE: setting a
+ * state while bs_set_sampling holds top_k > 1 (and bs_set_sampling(top_k > 1) while a row holds state; BS_STEP_VERIFY
+ * on a row with state).  The first call allocates the table, the selection histograms, the read-outs and, if absent,
+ * the [max_batch][vocab] logits buffer, counted under workspace_bytes from then on. */
+int bs_set_row_sampler(bs_stage *stage, int32_t slot, int32_t count, const bs_row_sampler *params, void *stream);
+/* Run the row sampler -- the kernels the tail runs -- on caller-given fp32 logits [batch][ld] (ld >= vocab; device, or
+ * host with BS_STEP_HOST_IO in flags, then tokens is host too and the call synchronises) for rows [slot, slot +
+ * batch) at positions[b] (host).  Rows without state take the first index of the largest logit.  Touches no KV row
+ * and no cached position.  Statuses as bs_set_row_sampler; allocates like it on first use. */
+int bs_sample_logits(bs_stage *stage, int32_t slot, int32_t batch, const int32_t *positions, const float *logits,
+                     int32_t ld, int32_t *tokens, int32_t flags, void *stream);
+/* Read-out of row `slot`'s last draw, for verification (synchronises the device), like bs_read_head_screen.
+ * BS_ERR_STATE on a stage that never ran the row sampler. */
+int bs_read_row_draw(bs_stage *stage, int32_t slot, bs_row_draw *out);
+
 /* Decode steps (S = 1) and BS_STEP_VERIFY passes on device buffers are captured once per shape into a hipGraph and replayed
  * (the default, on = 1); on = 0 launches them eagerly every step (same kernels, same results: for
  * debugging and A/B timing).  Drops captured graphs.  Returns BS_OK.  A stage starts with graphs off
