@@ -211,18 +211,25 @@ struct RowDrawDev {     // the layout of bs_row_draw
   int token, position;
 };
 struct RsState;
+// The table is indexed by KV row; everything else by scratch lane.  The plain tail and bs_sample_logits use lane =
+// KV row (one selection per row); a verify-draw pass has its own scratch of kVerifyMaxTokens lanes, one per position.
 struct RowSampleBufs {
   RowSamplerDev* table;        // [max_batch]
-  unsigned long long* rowmax;  // [max_batch] max (key << 32 | ~index) of the step (zero between steps)
-  uint32_t* hcnt;              // [max_batch][6][2048] count histograms of the six digit passes (zero between steps)
-  unsigned long long* hmass;   // [max_batch][3][2048] fixed-point mass histograms of the last three
-  RowDrawDev* draw;            // [max_batch] read-out of each row's last draw
-  RsState* st;                 // [max_batch][6] what one launch hands to the next
+  unsigned long long* rowmax;  // [lanes] max (key << 32 | ~index) of the step (zero between steps)
+  uint32_t* hcnt;              // [lanes][6][2048] count histograms of the six digit passes (zero between steps)
+  unsigned long long* hmass;   // [lanes][3][2048] fixed-point mass histograms of the last three
+  RowDrawDev* draw;            // [lanes] read-out of each lane's last draw
+  RsState* st;                 // [lanes][6] what one launch hands to the next
+  int* pos;                    // [lanes] draw positions of a verify-draw pass (null in the per-row scratch)
 };
-// Bytes of all of the above for max_batch rows; offsets[6] receives where each array starts.  The buffer must be
-// zero before the first launch_row_sample.
+// Bytes of all of the above but pos for `lanes` lanes (and a table of as many rows); offsets[6] receives where each
+// array starts.  The buffer must be zero before the first launch.
 size_t row_sample_bytes(int max_batch, size_t* offsets);
 RowSampleBufs row_sample_bufs(char* base, const size_t* offsets);
+// The scratch of a verify-draw pass: row_sample_bytes(kVerifyMaxTokens) plus the positions; row_sample_verify_bufs
+// takes the table from `rows`.
+size_t row_sample_verify_bytes(size_t* offsets);
+RowSampleBufs row_sample_verify_bufs(const RowSampleBufs& rows, char* base, const size_t* offsets);
 // table[slot .. slot + n) = rows[0..n) (host), stream ordered, by kernel arguments (set_past_kernel's pattern).
 void launch_row_table(const RowSampleBufs& rb, int slot, const RowSamplerDev* rows, int n, hipStream_t s);
 // Sample (or, for rows without state, take the first index of the largest logit of) rows [slot, slot + B) from
@@ -230,6 +237,12 @@ void launch_row_table(const RowSampleBufs& rb, int slot, const RowSamplerDev* ro
 // null, past_dev[b] + seq.  The last launch writes tokens[b], the row's read-out and past_adv[b] += seq (optional).
 void launch_row_sample(const RowSampleBufs& rb, const float* logits, int ld, int V, int slot, int B,
                        const int* positions, const int* past_dev, int seq, int* tokens, int* past_adv, hipStream_t s);
+// The tail of a verify-draw pass: M = B * S <= kVerifyMaxTokens selections, the same seven launches.  Selection m
+// reads logits row m with the state of table row slot + m / S, works in lane m of `vb` (row_sample_verify_bufs) and
+// draws at position past_dev[m / S] + m % S + 1 (fixed by the first launch in vb.pos, so the last one may advance
+// past_dev); tokens[m] and vb.draw[m] receive the result.  One thread per KV row does past_adv[b] += S (optional).
+void launch_row_sample_verify(const RowSampleBufs& vb, const float* logits, int ld, int V, int slot, int B, int S,
+                              const int* past_dev, int* tokens, int* past_adv, hipStream_t s);
 
 // ---- Weight-only int8 (bf16 stages with BS_FLAG_INT8_WEIGHTS; kernels.hip "Weight-only int8") ----
 // Q[n][k] = rne(W[n][k] / scale[n]), scale[n] = max_k |W[n][k]| / 127 (1 for a zero row); W bf16 [N][K].

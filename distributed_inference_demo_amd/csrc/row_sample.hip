@@ -22,6 +22,14 @@
 // "Resolve" walks a 2048-bin histogram from the top bin down until the running sum reaches the target; every block of
 // the row does it for itself (a few KB out of L2) and block 0 records the result for the next launch.  A row without
 // sampler state runs stage 0 and the pick only and gets the first index of its largest logit.
+//
+// A selection has three indices: the table row whose state it uses, the logits row it reads and the scratch lane it
+// works in.  The plain tail and bs_sample_logits make one selection per KV row (lane = table row = slot + b).  The
+// tail of a verify-draw pass makes B * S of them, S per KV row, in a scratch of its own: selection m uses table row
+// slot + m / S and lane m, and draws at position past_dev[m / S] + m % S + 1.  Stage 0 fixes that position in the
+// lane (pos), because the pick of the row's last position advances past_dev while the picks of its other positions
+// run.  The per-row scratch is never touched by a verify-draw pass, so a plain step between two passes finds its
+// histograms zero.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -152,13 +160,13 @@ __device__ __forceinline__ uint32_t rs_prefix_of(uint32_t key, int lvl) { return
 
 __device__ __forceinline__ bool rs_topk_on(const RowSamplerDev& p, int V) { return p.active && p.top_k > 0 && p.top_k < V; }
 
-// Resolve histogram `j` (0..5) of the row from the state before it; wave 0 computes, everyone gets it through LDS.
+// Resolve histogram `j` (0..5) of the lane from the state before it; wave 0 computes, everyone gets it through LDS.
 // sval / scnt: LDS [kBins] scratch.  Call with the whole block.
-__device__ void rs_advance(const RowSampleBufs& rb, int row, int j, const RowSamplerDev& p, const RsState& ps, u64* sval,
+__device__ void rs_advance(const RowSampleBufs& rb, int lane, int j, const RowSamplerDev& p, const RsState& ps, u64* sval,
                            uint32_t* scnt, RsState* out) {
   const int tid = threadIdx.x;
-  const uint32_t* hc = rb.hcnt + ((size_t)row * 6 + j) * kBins;
-  const u64* hm = j >= 3 ? rb.hmass + ((size_t)row * 3 + (j - 3)) * kBins : nullptr;
+  const uint32_t* hc = rb.hcnt + ((size_t)lane * 6 + j) * kBins;
+  const u64* hm = j >= 3 ? rb.hmass + ((size_t)lane * 3 + (j - 3)) * kBins : nullptr;
   for (int i = tid; i < kBins; i += kThreads) {
     const uint32_t c = hc[i];
     scnt[i] = c;
@@ -195,16 +203,22 @@ __device__ void rs_advance(const RowSampleBufs& rb, int row, int j, const RowSam
   __syncthreads();
 }
 
+// Where selection m (the block's y or x index) finds its state, its scratch and its logits: table row slot + m / per,
+// lane lane0 + m, logits row m.  per == 1 and lane0 == slot: one selection per KV row in the row's own lane.
+struct RsMap { int slot, lane0, per; };
+
 __global__ __launch_bounds__(kThreads) void row_level_kernel(RowSampleBufs rb, const float* __restrict__ logits, int ld,
-                                                             int V, int slot, int stage) {
+                                                             int V, RsMap mp, int stage, const int* past_dev) {
   __shared__ u64 sval[kBins];
   __shared__ uint32_t scnt[kBins];
   __shared__ RsState cur;
   __shared__ u64 red[16];
-  const int b = blockIdx.y, row = slot + b, tid = threadIdx.x;
+  const int m = blockIdx.y, row = mp.slot + m / mp.per, lane = mp.lane0 + m, tid = threadIdx.x;
   const RowSamplerDev p = rb.table[row];
-  const float* lr = logits + (size_t)b * ld;
+  const float* lr = logits + (size_t)m * ld;
   const bool topk = rs_topk_on(p, V);
+  // a verify-draw pass: the draw position of this selection, read by the pick (which advances past_dev)
+  if (stage == 0 && rb.pos && blockIdx.x == 0 && tid == 0) rb.pos[lane] = past_dev[m / mp.per] + m % mp.per + 1;
   if (stage > 0 && !p.active) return;
   if (stage > 0 && stage < 3 && !topk) return;
 
@@ -226,10 +240,10 @@ __global__ __launch_bounds__(kThreads) void row_level_kernel(RowSampleBufs rb, c
     __syncthreads();
     if (tid == 0) {
       for (int w = 1; w < kThreads / 64; w++) best = red[w] > best ? red[w] : best;
-      atomicMax(rb.rowmax + row, best);
+      atomicMax(rb.rowmax + lane, best);
     }
     if (topk) {
-      uint32_t* hc = rb.hcnt + ((size_t)row * 6 + 0) * kBins;
+      uint32_t* hc = rb.hcnt + ((size_t)lane * 6 + 0) * kBins;
       for (int i = tid; i < kBins; i += kThreads)
         if (scnt[i]) atomicAdd(hc + i, scnt[i]);
     }
@@ -242,11 +256,11 @@ __global__ __launch_bounds__(kThreads) void row_level_kernel(RowSampleBufs rb, c
     if (tid == 0) cur = ps;  // every key is a candidate
     __syncthreads();
   } else {
-    if (stage != 1) ps = rb.st[(size_t)row * 6 + stage - 1];
-    rs_advance(rb, row, stage - 1, p, ps, sval, scnt, &cur);
+    if (stage != 1) ps = rb.st[(size_t)lane * 6 + stage - 1];
+    rs_advance(rb, lane, stage - 1, p, ps, sval, scnt, &cur);
   }
   const RsState st = cur;
-  if (blockIdx.x == 0 && tid == 0) rb.st[(size_t)row * 6 + stage] = st;
+  if (blockIdx.x == 0 && tid == 0) rb.st[(size_t)lane * 6 + stage] = st;
   __syncthreads();  // sval / scnt are reused below
 
   // histogram of this stage's digit under the chosen prefix
@@ -254,7 +268,7 @@ __global__ __launch_bounds__(kThreads) void row_level_kernel(RowSampleBufs rb, c
   const bool mass = stage >= 3;
   for (int i = tid; i < kBins; i += kThreads) { scnt[i] = 0; sval[i] = 0; }
   __syncthreads();
-  const float lmax = rs_unkey((uint32_t)(rb.rowmax[row] >> 32));
+  const float lmax = rs_unkey((uint32_t)(rb.rowmax[lane] >> 32));
   for (int i = blockIdx.x * kThreads + tid; i < V; i += gridDim.x * kThreads) {
     const float l = lr[i];
     const uint32_t key = rs_key(l);
@@ -265,8 +279,8 @@ __global__ __launch_bounds__(kThreads) void row_level_kernel(RowSampleBufs rb, c
     if (mass) atomicAdd(&sval[d], rs_weight(l, lmax, p.temperature));
   }
   __syncthreads();
-  uint32_t* hc = rb.hcnt + ((size_t)row * 6 + stage) * kBins;
-  u64* hm = mass ? rb.hmass + ((size_t)row * 3 + (stage - 3)) * kBins : nullptr;
+  uint32_t* hc = rb.hcnt + ((size_t)lane * 6 + stage) * kBins;
+  u64* hm = mass ? rb.hmass + ((size_t)lane * 3 + (stage - 3)) * kBins : nullptr;
   for (int i = tid; i < kBins; i += kThreads)
     if (scnt[i]) {
       atomicAdd(hc + i, scnt[i]);
@@ -276,10 +290,11 @@ __global__ __launch_bounds__(kThreads) void row_level_kernel(RowSampleBufs rb, c
 
 struct RsPositions { int v[64]; };
 
-// One block per row: the step's last kernel.  positions: by value when use_pos (bs_sample_logits), else
-// past_dev[b] + seq; past_adv (optional): past_adv[b] += seq.
+// One block per selection: the step's last kernel.  positions: by value when use_pos (bs_sample_logits), the lane's
+// rb.pos where the scratch has one (a verify-draw pass), else past_dev[b] + seq; past_adv (optional): the block of
+// the last selection of every KV row does past_adv[m / per] += seq.
 __global__ __launch_bounds__(kThreads) void row_pick_kernel(RowSampleBufs rb, const float* __restrict__ logits, int ld,
-                                                            int V, int slot, RsPositions pos, int use_pos,
+                                                            int V, RsMap mp, RsPositions pos, int use_pos,
                                                             const int* past_dev, int seq, int* __restrict__ tokens,
                                                             int* past_adv) {
   __shared__ u64 sval[kBins];
@@ -287,11 +302,12 @@ __global__ __launch_bounds__(kThreads) void row_pick_kernel(RowSampleBufs rb, co
   __shared__ RsState cur;
   __shared__ u64 wtot[kThreads / 64];
   __shared__ int found;
-  const int b = blockIdx.x, row = slot + b, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, row = mp.slot + b / mp.per, sl = mp.lane0 + b, tid = threadIdx.x, lane = tid & 63,
+            wave = tid >> 6;
   const RowSamplerDev p = rb.table[row];
   const float* lr = logits + (size_t)b * ld;
-  const u64 rmax = rb.rowmax[row];
-  const int position = use_pos ? pos.v[b] : past_dev[b] + seq;
+  const u64 rmax = rb.rowmax[sl];
+  const int position = use_pos ? pos.v[b] : (rb.pos ? rb.pos[sl] : past_dev[b] + seq);
   const int greedy = (int)(0xFFFFFFFFu - (uint32_t)(rmax & 0xFFFFFFFFull));
   const float lmax = rs_unkey((uint32_t)(rmax >> 32));
   RowDrawDev out{};
@@ -300,8 +316,8 @@ __global__ __launch_bounds__(kThreads) void row_pick_kernel(RowSampleBufs rb, co
   if (!p.active) {
     out.threshold = lmax; out.token = greedy;
   } else {
-    const RsState ps = rb.st[(size_t)row * 6 + 5];
-    rs_advance(rb, row, 5, p, ps, sval, scnt, &cur);
+    const RsState ps = rb.st[(size_t)sl * 6 + 5];
+    rs_advance(rb, sl, 5, p, ps, sval, scnt, &cur);
     const RsState st = cur;
     const uint32_t tkey = st.prefix;
     const u64 massN = st.mass_above;
@@ -355,17 +371,17 @@ __global__ __launch_bounds__(kThreads) void row_pick_kernel(RowSampleBufs rb, co
     token = found >= 0 ? found : greedy;  // target < mass(N): always found
     out.threshold = rs_unkey(tkey); out.n_nucleus = (int)st.cnt_above; out.n_candidates = (int)st.nC;
     out.u24 = u24; out.mass_nucleus = massN; out.mass_candidates = st.massC; out.token = token;
-    // the row's histograms back to zero for the next step (stream-ordered behind every reader)
-    uint32_t* hc = rb.hcnt + (size_t)row * 6 * kBins;
-    u64* hm = rb.hmass + (size_t)row * 3 * kBins;
+    // the lane's histograms back to zero for the next step (stream-ordered behind every reader)
+    uint32_t* hc = rb.hcnt + (size_t)sl * 6 * kBins;
+    u64* hm = rb.hmass + (size_t)sl * 3 * kBins;
     for (int i = tid; i < 6 * kBins; i += kThreads) hc[i] = 0;
     for (int i = tid; i < 3 * kBins; i += kThreads) hm[i] = 0;
   }
   if (tid == 0) {
     tokens[b] = token;
-    rb.draw[row] = out;
-    rb.rowmax[row] = 0;
-    if (past_adv) past_adv[b] += seq;
+    rb.draw[sl] = out;
+    rb.rowmax[sl] = 0;
+    if (past_adv && b % mp.per == mp.per - 1) past_adv[b / mp.per] += seq;  // once per KV row
   }
 }
 
@@ -395,7 +411,20 @@ RowSampleBufs row_sample_bufs(char* base, const size_t* offsets) {
   rb.hmass = (unsigned long long*)(base + offsets[3]);
   rb.draw = (RowDrawDev*)(base + offsets[4]);
   rb.st = (RsState*)(base + offsets[5]);
+  rb.pos = nullptr;
   return rb;
+}
+
+size_t row_sample_verify_bytes(size_t* offsets) {
+  offsets[6] = row_sample_bytes(kVerifyMaxTokens, offsets);  // its table part stays unused
+  return offsets[6] + (size_t)kVerifyMaxTokens * 4;
+}
+
+RowSampleBufs row_sample_verify_bufs(const RowSampleBufs& rows, char* base, const size_t* offsets) {
+  RowSampleBufs vb = row_sample_bufs(base, offsets);
+  vb.table = rows.table;
+  vb.pos = (int*)(base + offsets[6]);
+  return vb;
 }
 
 void launch_row_table(const RowSampleBufs& rb, int slot, const RowSamplerDev* rows, int n, hipStream_t s) {
@@ -412,14 +441,26 @@ void launch_row_sample(const RowSampleBufs& rb, const float* logits, int ld, int
   if (B <= 0) return;
   const int nb = std::min(64, std::max(1, (V + 2 * kThreads - 1) / (2 * kThreads)));
   for (int stage = 0; stage < 6; stage++)
-    row_level_kernel<<<dim3(nb, B), kThreads, 0, s>>>(rb, logits, ld, V, slot, stage);
+    row_level_kernel<<<dim3(nb, B), kThreads, 0, s>>>(rb, logits, ld, V, RsMap{slot, slot, 1}, stage, nullptr);
   for (int i = 0; i < B; i += 64) {  // positions travel by value, 64 rows a launch
     RsPositions pos{};
     const int c = std::min(64, B - i);
     if (positions)
       for (int j = 0; j < c; j++) pos.v[j] = positions[i + j];
-    row_pick_kernel<<<c, kThreads, 0, s>>>(rb, logits + (size_t)i * ld, ld, V, slot + i, pos, positions ? 1 : 0,
+    row_pick_kernel<<<c, kThreads, 0, s>>>(rb, logits + (size_t)i * ld, ld, V, RsMap{slot + i, slot + i, 1}, pos,
+                                           positions ? 1 : 0,
                                            past_dev ? past_dev + i : nullptr, seq, tokens + i,
                                            past_adv ? past_adv + i : nullptr);
   }
+}
+
+void launch_row_sample_verify(const RowSampleBufs& vb, const float* logits, int ld, int V, int slot, int B, int S,
+                              const int* past_dev, int* tokens, int* past_adv, hipStream_t s) {
+  const int M = B * S;
+  if (M <= 0 || M > kVerifyMaxTokens || !vb.pos) return;  // the scratch holds kVerifyMaxTokens lanes
+  const int nb = std::min(64, std::max(1, (V + 2 * kThreads - 1) / (2 * kThreads)));
+  const RsMap mp{slot, 0, S};
+  for (int stage = 0; stage < 6; stage++)
+    row_level_kernel<<<dim3(nb, M), kThreads, 0, s>>>(vb, logits, ld, V, mp, stage, past_dev);
+  row_pick_kernel<<<M, kThreads, 0, s>>>(vb, logits, ld, V, mp, RsPositions{}, 0, past_dev, S, tokens, past_adv);
 }

@@ -66,7 +66,8 @@ static bool is_matrix(int t) { return t == T_QKV_W || t == T_DENSE_W || t == T_F
 
 struct GraphKey {
   int B, seq, slot, flags;
-  int rows;  // the tail runs the per-row sampler (a row of the call holds sampler state)
+  int rows;  // the tail runs the per-row sampler (a row of the call holds sampler state); with BS_STEP_VERIFY_DRAW
+             // in flags, the verify tail draws at every position
   const void* in;
   void* out;
   float* logits;
@@ -210,6 +211,14 @@ struct bs_stage {
   RowSampleBufs rs{};
   std::vector<RowSamplerDev> rs_host;  // [max_batch]
   int rs_active = 0;                   // rows that hold state
+  // BS_STEP_VERIFY_DRAW: the sampler scratch of kVerifyMaxTokens positions (vd_base, made by the first verify-draw
+  // pass that runs the sampler) and the [max(max_batch, kVerifyMaxTokens)][V] logits its tail reads when the caller
+  // gives no device logits (vd_logits, made by the first such pass); vd_last_*: the shape of the last such pass
+  char* vd_base = nullptr;
+  size_t vd_bytes = 0;                 // vd_base and vd_logits
+  RowSampleBufs vd{};
+  float* vd_logits = nullptr;
+  int vd_last_slot = 0, vd_last_B = 0, vd_last_S = 0;  // B == 0: no verify-draw pass ran
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -351,6 +360,8 @@ static void free_stage(bs_stage* s) {
   if (s->sc_base) hipFree(s->sc_base);
   if (s->vf_base) hipFree(s->vf_base);
   if (s->rs_base) hipFree(s->rs_base);
+  if (s->vd_base) hipFree(s->vd_base);
+  if (s->vd_logits) hipFree(s->vd_logits);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
@@ -797,7 +808,7 @@ extern "C" int bs_stage_info(const bs_stage* s, bs_stage_desc* d, uint64_t* wb, 
   if (wb) *wb = s->wbytes;
   if (kvb) *kvb = s->kvbytes;
   // the head-screening shadow copy, the int8 KV staging, the scoring and the verify buffers count as workspace
-  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + s->vf_bytes + s->rs_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
+  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + s->vf_bytes + s->rs_bytes + s->vd_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
   return BS_OK;
 }
 
@@ -1194,6 +1205,11 @@ static bool rows_sampled(const bs_stage* s, int slot, int B) {
   return false;
 }
 
+// Does a verify pass with these flags end in the row sampler at every position (else the argmax tail)?
+static bool verify_draws(const bs_stage* s, int flags, int slot, int B) {
+  return (flags & BS_STEP_VERIFY) && (flags & BS_STEP_VERIFY_DRAW) && s->d.is_last && rows_sampled(s, slot, B);
+}
+
 // Does a forward of B rows at `slot` take the screened greedy tail (else the full head)?
 static bool head_screened(const bs_stage* s, int slot, int B, bool want_logits) {
   return s->hs_on && s->hs_base && s->d.is_last && !s->n_labels && s->top_k <= 1 && !want_logits &&
@@ -1379,6 +1395,9 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     // verify tail: ln_f of all M positions, the tied lm_head with the argmax epilogue over M rows (never screened),
     // the first index of the largest logit at every position; the finalize is the pass's last kernel and advances
     // past_dev by S for the B rows
+    // BS_STEP_VERIFY_DRAW on rows with sampler state: the head writes the logits of all M positions and the row
+    // sampler draws each of them (row_sample.hip); its pick is the pass's last kernel and advances past_dev once a row
+    const bool draws = verify_draws(s, step->flags, slot, B);
     Epi e{};
     e.kind = EPI_ARGMAX; e.keys = s->vf_keys; e.logits = want_logits && !host_io ? logits : nullptr; e.ldo = V;
     float* dev_logits = nullptr;
@@ -1387,9 +1406,13 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
       if (rc != BS_OK) return rc;
       e.logits = dev_logits;
     }
+    if (draws && !e.logits) e.logits = s->vd_logits;
     int* tok_out = host_io ? s->vf_tok : (int*)out;
     linear_ln(s, st, cur, 1, 0, s->lnf_g, s->lnf_b, WMat{s->wemb}, M, V, h, with_splitk(s, e), 0);
-    launch_argmax_finalize(s->vf_keys, M, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S, B);
+    if (draws)
+      launch_row_sample_verify(s->vd, e.logits, V, V, slot, B, S, past_dev, tok_out, s->past_dev, st);
+    else
+      launch_argmax_finalize(s->vf_keys, M, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S, B);
     if (host_io) {
       HIP_TRY(hipMemcpyAsync(out, s->vf_tok, (size_t)M * 4, hipMemcpyDeviceToHost, st));
       if (dev_logits) HIP_TRY(hipMemcpyAsync(logits, dev_logits, (size_t)M * V * 4, hipMemcpyDeviceToHost, st));
@@ -1607,6 +1630,46 @@ extern "C" int bs_read_row_draw(bs_stage* s, int32_t slot, bs_row_draw* out) {
   return BS_OK;
 }
 
+// The scratch of a verify-draw pass (first use) and, when the pass has no other device logits to write, its own
+// logits buffer (first such use).  Zeroed on the stage's own stream and synchronised, like the per-row scratch.
+static int verify_draw_buffers(bs_stage* s, bool need_logits) {
+  if (!s->vd_base) {
+    size_t off[7];
+    const size_t bytes = row_sample_verify_bytes(off);
+    char* base = nullptr;
+    if (hipMalloc((void**)&base, bytes) != hipSuccess)
+      return fail(BS_ERR_OOM, "verify-draw sampler scratch allocation failed (" + std::to_string(bytes) + " B)");
+    if (hipMemsetAsync(base, 0, bytes, s->own) != hipSuccess || hipStreamSynchronize(s->own) != hipSuccess) {
+      hipFree(base);
+      return fail(BS_ERR_DEVICE, "verify-draw sampler scratch memset");
+    }
+    s->vd_base = base;
+    s->vd_bytes += bytes;
+    s->vd = row_sample_verify_bufs(s->rs, base, off);
+  }
+  if (need_logits && !s->vd_logits) {
+    const size_t lb = (size_t)std::max(s->d.max_batch, kVerifyMaxTokens) * s->d.vocab * 4;
+    if (hipMalloc((void**)&s->vd_logits, lb) != hipSuccess) {
+      s->vd_logits = nullptr;
+      return fail(BS_ERR_OOM, "verify-draw logits allocation failed (" + std::to_string(lb) + " B)");
+    }
+    s->vd_bytes += lb;
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_read_verify_draw(bs_stage* s, int32_t slot, int32_t t, bs_row_draw* out) {
+  if (!s || !out) return fail(BS_ERR_INVALID, "stage/out is NULL");
+  if (!s->vd_last_B) return fail(BS_ERR_STATE, "the stage never ran a verify-draw pass");
+  if (slot < s->vd_last_slot || slot >= s->vd_last_slot + s->vd_last_B || t < 0 || t >= s->vd_last_S)
+    return fail(BS_ERR_INVALID, "row or position outside the last verify-draw pass");
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, s->vd.draw + (size_t)(slot - s->vd_last_slot) * s->vd_last_S + t, sizeof(*out),
+                    hipMemcpyDeviceToHost));
+  return BS_OK;
+}
+
 extern "C" int bs_set_graphs(bs_stage* s, int32_t on) {
   if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
   HIP_TRY(hipSetDevice(s->d.device));
@@ -1667,6 +1730,9 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
                                           std::to_string(s->kv_stage_cap) + " (max(max_tokens, max_ctx))");
   }
   const bool verify = (step->flags & BS_STEP_VERIFY) != 0;
+  const bool draw = (step->flags & BS_STEP_VERIFY_DRAW) != 0;
+  if (draw && (sc || !verify))
+    return fail(BS_ERR_INVALID, "BS_STEP_VERIFY_DRAW is valid only together with BS_STEP_VERIFY on bs_forward");
   if (verify) {
     if (sc) return fail(BS_ERR_INVALID, "BS_STEP_VERIFY is not valid for a scoring pass");
     if (S < 2 || S > 8 || M > kVerifyMaxTokens)
@@ -1677,7 +1743,8 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     if (s->top_k > 1) return fail(BS_ERR_STATE, "BS_STEP_VERIFY needs the greedy pick (bs_set_sampling top_k <= 1)");
     if (d.is_last && (!s->wemb || s->hv0 != 0 || s->hv1 != d.vocab))
       return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a last stage needs the whole lm_head");
-    if (rows_sampled(s, slot, B)) return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a row that holds sampler state");
+    if (!draw && rows_sampled(s, slot, B))
+      return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a row that holds sampler state (BS_STEP_VERIFY_DRAW draws from it)");
   }
   if (!in || (!out && !sc)) return fail(BS_ERR_INVALID, "in/out is NULL");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
@@ -1708,6 +1775,11 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     s->vf_ml = (float*)(s->vf_base + vo[1]);
     s->vf_keys = (unsigned long long*)(s->vf_base + vo[2]);
     s->vf_tok = (int*)(s->vf_base + vo[3]);
+  }
+  const bool draws = verify_draws(s, step->flags, slot, B);
+  if (draws) {
+    int rc = verify_draw_buffers(s, !want_logits);  // host-I/O logits go through the logits staging
+    if (rc != BS_OK) return rc;
   }
 
   // Decode steps and verify passes on device buffers replay a captured hipGraph: the kernels read past_len from
@@ -1765,6 +1837,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
   s->hs_last_rows = !sc && !verify && head_screened(s, slot, B, want_logits) ? B : 0;
+  if (draws) { s->vd_last_slot = slot; s->vd_last_B = B; s->vd_last_S = S; }
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)
     s->past_next.assign(pasts.begin(), pasts.end());
     for (int& p : s->past_next) p += S;

@@ -41,6 +41,10 @@ decoding.cpp:24-66): the last rank gives the row a sample is admitted into the s
 request_seed(--sample-seed, sample id)) just before the sample's prefill pass, so its first generated token is already
 sampled.  A draw depends on (seed, position, logits) only, never on the row.  The whole lm_head stays on the last
 stage (no head ring).
+--sample --sample-speculate K is sampled speculative decoding on one GPU: --speculate's loop with the row's sampler
+state set before each sample's prefill and verify passes that return the row's own draw at every position
+(BS_STEP_VERIFY_DRAW).  The tokens are plain sampled decoding's for the same state and seed; a draft model holds the
+same state, so it draws with the target's u at every position.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
 unseeded top-k, token ids in (no tokenizer).
@@ -88,6 +92,7 @@ class RunConfig:
     top_p: float = 1.0            # sampling: the nucleus' share of the candidates' mass, in (0, 1]
     temperature: float = 1.0      # sampling: > 0
     sample_seed: int = 0          # sampling: sample i draws with request_seed(sample_seed, i)
+    sample_speculate: int = 0     # sampled speculative decoding: tokens drafted per verify-draw pass (0 = off; needs sample)
 
     def __post_init__(self):
         if self.kv not in ("bf16", "int8"):
@@ -110,6 +115,14 @@ class RunConfig:
                 raise ValueError("sampling needs top_k >= 0, top_p in (0, 1] and a positive finite temperature "
                                  f"(got {self.top_k}, {self.top_p}, {self.temperature})")
             self.head_split = False
+        if self.sample_speculate:
+            if not self.sample:
+                raise ValueError("sample_speculate is sampled speculative decoding: it needs sample (greedy: speculate)")
+            if not 1 <= self.sample_speculate <= 7:
+                raise ValueError(f"sample_speculate must be in [1, 7] (got {self.sample_speculate}): a verify pass "
+                                 "holds 8 positions")
+            if self.kv != "bf16":
+                raise ValueError("sampled speculative decoding needs kv = 'bf16' (no verify pass over an int8 KV cache yet)")
 
 
 def request_seed(sample_seed, i):
@@ -154,7 +167,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     lengths (None: synthetic).  Returns {"samples": [[max_length ids] per sample], ...} on rank 0,
     None elsewhere.  Collective: every rank calls it with the same cfg."""
     say = log if (log is not None and rank == 0) else (lambda *_: None)
-    if cfg.speculate and world != 1:
+    if (cfg.speculate or cfg.sample_speculate) and world != 1:
         raise ValueError("speculative decoding runs on one stage (world == 1): acceptance is data-dependent, the "
                          "pipeline's schedule is not")
     if cfg.sample and executor_factory is not None:
@@ -181,7 +194,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
         return _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.max_length == 0:
         return _classify_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
-    if cfg.speculate:
+    if cfg.speculate or cfg.sample_speculate:
         return _spec_run(cfg, model, device, prompts, lens, say)
     # samples in flight = n_mb micro-batches x mb rows: one micro-batch per stage keeps every stage
     # busy; the rest of the pool rides as rows of a micro-batch (one GPU: one batched decode)
@@ -390,8 +403,10 @@ def _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory,
 
 def _spec_run(cfg, model, device, prompts, lens, say):
     """--speculate K (world == 1): the whole model as one stage, the samples decoded one after another in KV row 0
-    by speculative.SpeculativeDecoder.  Returns the generation task's record plus the acceptance statistics."""
-    from .speculative import NgramDrafter, SpeculativeDecoder, StageDrafter
+    by speculative.SpeculativeDecoder.  Returns the generation task's record plus the acceptance statistics.
+    --sample --sample-speculate K: the same loop, sample i decoded with the sampler state of the config and
+    request_seed(sample_seed, i); a model drafter holds the same state."""
+    from .speculative import NgramDrafter, SpeculativeDecoder, StageChain, StageDrafter
     from .stage import Stage
     dev = device.index if device.type == "cuda" and device.index is not None else 0
     max_ctx = max(lens) + cfg.max_length + 1
@@ -401,23 +416,30 @@ def _spec_run(cfg, model, device, prompts, lens, say):
                      max_ctx=max_ctx, max_tokens=max(lens) + 32, seed=cfg.seed, int8_weights=m.int8_weights,
                      mxfp4_weights=m.mxfp4_weights)
 
+    k = cfg.sample_speculate or cfg.speculate
+    sampling = ({"top_k": cfg.top_k, "top_p": cfg.top_p, "temperature": cfg.temperature} if cfg.sample_speculate
+                else None)
     if cfg.draft == "ngram":
-        drafter = NgramDrafter(cfg.speculate)
+        drafter = NgramDrafter(k)
     else:
         dm = config.get(cfg.draft) if isinstance(cfg.draft, str) else cfg.draft
         if dm.vocab != model.vocab:
             raise ValueError(f"draft model {dm.name} has another vocabulary ({dm.vocab}) than {model.name} ({model.vocab})")
-        drafter = StageDrafter([whole(dm)], cfg.speculate)
-    dec = SpeculativeDecoder([whole(model)], drafter, cfg.speculate)
-    say(STATES[0], {"rank_layers": [0, model.n_layer], "stages": 1, "speculate": cfg.speculate, "draft": cfg.draft})
+        drafter = StageDrafter([whole(dm)], k)
+    chain = StageChain([whole(model)])
+    say(STATES[0], {"rank_layers": [0, model.n_layer], "stages": 1, "speculate": k, "draft": cfg.draft,
+                    **({"sample": True} if sampling else {})})
     say(STATES[1], {"num_sample": cfg.num_sample, "max_length": cfg.max_length})
     out, tot = [], {"passes": 0, "drafted": 0, "accepted": 0, "plain_steps": 0}
     t_start = time.perf_counter()
-    for p in prompts:
-        toks, st = dec.generate(p, cfg.max_length)
+    for i, p in enumerate(prompts):
+        sampler = dict(sampling, seed=request_seed(cfg.sample_seed, i)) if sampling else None
+        if sampler and isinstance(drafter, StageDrafter):
+            drafter.chain.set_sampler(sampler)  # the draft row draws with this request's u
+        toks, st = SpeculativeDecoder(chain, drafter, k, sampler=sampler).generate(p, cfg.max_length)
         out.append(toks)
-        for k in tot:
-            tot[k] += st[k]
+        for name in tot:
+            tot[name] += st[name]
     if device.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t_start
@@ -425,6 +447,8 @@ def _spec_run(cfg, model, device, prompts, lens, say):
            "core_pool_size": cfg.core_pool_size, "stages": 1, "prompt_lens": lens, "seconds": dt,
            "tokens_per_s": cfg.num_sample * cfg.max_length / dt, "speculate": cfg.speculate, "draft": cfg.draft, **tot,
            "acceptance_rate": tot["accepted"] / tot["drafted"] if tot["drafted"] else None}
+    if sampling:
+        res.update(sample=True, sample_seed=cfg.sample_seed, sample_speculate=k, **sampling)
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
     say(STATES[3], {})
     return res

@@ -10,6 +10,14 @@ exactly the tokens plain greedy decoding produces.
                                   variant of the target) with its own KV row
     SpeculativeDecoder(stages, drafter, k).generate(prompt, max_new)
 
+Sampled speculative decoding (sampler = {"top_k", "top_p", "temperature", "seed"} on the decoder, and on a
+StageDrafter): the target's KV row holds that per-row sampler state, plain steps sample, and a verify pass runs with
+BS_STEP_VERIFY_DRAW: it returns the row's own DRAW at every position.  A draw depends on (seed, position, logits)
+only, so the agreeing prefix of the draft plus one more token is exactly what plain sampled decoding emits --
+token-matching verification, no rejection-sampling arithmetic, the output distribution is plain sampling's.  A draft
+model that holds the same state draws with the target's u at every position, so its proposal agrees wherever the two
+models' CDF intervals of the token overlap at u.
+
 A drafter is any object with `propose(history, k) -> list of at most k token ids` (history: the prompt and every
 token emitted so far); an empty proposal makes the decoder take a plain S = 1 step.
 
@@ -86,14 +94,28 @@ class StageChain:
             b = self._buf[seq] = (ids, hid, out)
         return b
 
-    def _run(self, ids, past, verify):
+    def set_sampler(self, sampler):
+        """Row 0's sampler state on the last stage ({"top_k", "top_p", "temperature", "seed"}; missing keys take
+        set_row_sampler's defaults), or back to greedy with None.  Ordered on the chain's stream."""
+        last = self.stages[-1]
+        stream = None
+        if not self.host_io:
+            self._buffers(1)
+            stream = self._stream.cuda_stream
+        if sampler is None:
+            last.clear_row_sampler(0, stream=stream)
+        else:
+            last.set_row_sampler(0, stream=stream, **sampler)
+
+    def _run(self, ids, past, verify, draw=False):
         seq = len(ids)
+        kw = {"draw": True} if draw else {}  # stage objects without the flag are never handed it
         for st in self.stages:
             st.past[0] = past  # the rows' host mirrors follow the caller's position (Stage.rollback)
         if self.host_io:
             x = np.asarray(ids, np.int32).reshape(1, seq)
             for st in self.stages:
-                x = st.forward_host(x, 1, seq, slot=0, past_len=past, verify=verify)
+                x = st.forward_host(x, 1, seq, slot=0, past_len=past, verify=verify, **kw)
             return [int(t) for t in np.asarray(x).reshape(-1)]
         import torch
         dids, hid, out = self._buffers(seq)
@@ -102,7 +124,7 @@ class StageChain:
             x = dids
             for i, st in enumerate(self.stages):
                 y = out if i == len(self.stages) - 1 else hid[i]
-                st.forward(x, y, 1, seq, slot=0, past_len=past, stream=self._stream.cuda_stream, verify=verify)
+                st.forward(x, y, 1, seq, slot=0, past_len=past, stream=self._stream.cuda_stream, verify=verify, **kw)
                 x = y
             n = seq if verify else 1
             res = out[:n].cpu()  # a synchronous copy on the chain's stream
@@ -115,21 +137,26 @@ class StageChain:
     def step(self, tok, past):
         return self._run([tok], past, False)[0]
 
-    def verify(self, ids, past):
-        """Feed 2..8 tokens at position `past`; the greedy token after each of them."""
-        return self._run(list(ids), past, True)
+    def verify(self, ids, past, draw=False):
+        """Feed 2..8 tokens at position `past`; the greedy token after each of them, or with draw=True
+        (BS_STEP_VERIFY_DRAW) the row sampler's draw after each of them."""
+        return self._run(list(ids), past, True, draw)
 
 
 class StageDrafter:
     """k greedy S = 1 steps of a draft model: an in-process chain of stages with the target's vocabulary.  The draft
     keeps its own KV row: before drafting it rolls the row back to the prefix it shares with the history (the
-    accepted length) and catches up on the tokens it has not seen (one S = 1 step, or one short prefill pass)."""
+    accepted length) and catches up on the tokens it has not seen (one S = 1 step, or one short prefill pass).
+    sampler: the draft row holds this sampler state (the target's: same seed), so every draft is drawn with the
+    target's u at its position; None: greedy drafts."""
 
-    def __init__(self, stages, k, host_io=False):
+    def __init__(self, stages, k, host_io=False, sampler=None):
         if k < 1:
             raise ValueError("k must be >= 1")
         self.chain = stages if isinstance(stages, StageChain) else StageChain(stages, host_io=host_io)
         self.k = k
+        if sampler is not None:
+            self.chain.set_sampler(dict(sampler))
         self.fed = []  # the tokens whose K / V the draft's row holds
 
     def propose(self, history, k=None):
@@ -158,13 +185,18 @@ class SpeculativeDecoder:
     pass.  The prompt is prefilled through the unflagged path; each round the drafter proposes d <= k tokens and one
     BS_STEP_VERIFY pass of d + 1 positions emits accept()'s tokens; without a proposal the round is a plain S = 1
     step.  The tokens equal plain greedy decoding's whenever the target's top-2 logit margins exceed what the
-    batched and the single-row kernels may differ by (different summation orders)."""
+    batched and the single-row kernels may differ by (different summation orders).
+    sampler ({"top_k", "top_p", "temperature", "seed"}): sampled generation.  generate() sets row 0's sampler state
+    before the prefill (the first token is sampled), plain steps sample and verify passes return draws
+    (draw=True); accept() is unchanged.  The tokens equal plain sampled decoding's with that state wherever u lies
+    further inside the drawn token's CDF interval than the kernels' logit differences move its ends."""
 
-    def __init__(self, stages, drafter, k, host_io=False):
+    def __init__(self, stages, drafter, k, host_io=False, sampler=None):
         if not 1 <= k <= 7:
             raise ValueError("k must be in [1, 7] (a verify pass holds at most 8 positions)")
         self.chain = stages if isinstance(stages, StageChain) else StageChain(stages, host_io=host_io)
         self.drafter, self.k = drafter, k
+        self.sampler = None if sampler is None else dict(sampler)
 
     def generate(self, prompt, max_new):
         """Returns (tokens [max_new], {"passes": verify passes, "drafted": tokens proposed in them, "accepted":
@@ -175,6 +207,8 @@ class SpeculativeDecoder:
         if len(prompt) + max_new > self.chain.max_ctx:
             raise ValueError(f"prompt ({len(prompt)}) + max_new ({max_new}) exceed max_ctx ({self.chain.max_ctx})")
         stats = {"passes": 0, "drafted": 0, "accepted": 0, "plain_steps": 0}
+        if self.sampler is not None:
+            self.chain.set_sampler(self.sampler)
         hist = prompt + [self.chain.prefill(prompt, 0)]
         pos = len(prompt)  # positions the target's row holds; hist[pos:] is not cached yet (always one token)
         while len(hist) - len(prompt) < max_new:
@@ -186,7 +220,8 @@ class SpeculativeDecoder:
                 emitted = [self.chain.step(hist[-1], pos)]
                 stats["plain_steps"] += 1
             else:
-                top = self.chain.verify([hist[-1]] + draft, pos)
+                top = (self.chain.verify([hist[-1]] + draft, pos, draw=True) if self.sampler is not None
+                       else self.chain.verify([hist[-1]] + draft, pos))
                 n, emitted = accept(draft, top)
                 stats["passes"] += 1
                 stats["drafted"] += len(draft)

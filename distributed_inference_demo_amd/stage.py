@@ -40,6 +40,7 @@ BS_WEIGHTS_HOST = 1
 BS_STEP_HOST_IO = 1
 BS_STEP_LOGITS = 2
 BS_STEP_VERIFY = 4        # bs_step.flags: short verify pass (2 <= seq <= 8), greedy ids at every position
+BS_STEP_VERIFY_DRAW = 8   # bs_step.flags, with BS_STEP_VERIFY: the row sampler's draw at every position
 BS_FLAG_INT8_WEIGHTS = 1  # bs_stage_desc.flags: weight-only int8 block matrices
 BS_FLAG_CLASSIFIER = 2    # bs_stage_desc.flags: sequence-classification tail (score head, class ids out)
 BS_FLAG_INT8_KV = 4       # bs_stage_desc.flags: int8 KV cache, one fp32 scale per (position, head) vector
@@ -103,6 +104,7 @@ EXPORTS = [
     "bs_build_id", "bs_hbm_probe", "bs_mfma_probe", "bs_init_stage_file", "bs_weights_file_probe",
     "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
     "bs_forward_score", "bs_set_row_sampler", "bs_sample_logits", "bs_read_row_draw",
+    "bs_read_verify_draw",
 ]
 
 _LIB = None
@@ -159,6 +161,7 @@ def lib():
         L.bs_set_row_sampler.argtypes = [vp, i32, i32, ctypes.POINTER(RowSampler), vp]
         L.bs_sample_logits.argtypes = [vp, i32, i32, ctypes.POINTER(i32), vp, i32, vp, i32, vp]
         L.bs_read_row_draw.argtypes = [vp, i32, ctypes.POINTER(RowDraw)]
+        L.bs_read_verify_draw.argtypes = [vp, i32, i32, ctypes.POINTER(RowDraw)]
         L.bs_set_graphs.argtypes = [vp, i32]
         L.bs_set_head_screen.argtypes = [vp, i32]
         L.bs_read_head_screen.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(i32)]
@@ -283,13 +286,22 @@ class Stage:
         return st, pasts
 
     # ---- fast path (device pointers, stream ordered)
-    def forward(self, inp, out, batch, seq, slot=0, past_len=None, logits=None, stream=None, verify=False):
+    @staticmethod
+    def _verify_flags(verify, draw):
+        if draw and not verify:
+            raise ValueError("draw=True needs verify=True (BS_STEP_VERIFY_DRAW is a verify pass's flag)")
+        return (BS_STEP_VERIFY if verify else 0) | (BS_STEP_VERIFY_DRAW if draw else 0)
+
+    def forward(self, inp, out, batch, seq, slot=0, past_len=None, logits=None, stream=None, verify=False,
+                draw=False):
         """past_len: positions already cached, one int for every row or one per row (None: the
         host mirror of each row's position).
         verify: a BS_STEP_VERIFY pass (2 <= seq <= 8, batch * seq <= 32): the last stage writes int32 ids
         [batch][seq], the greedy token of every position (logits: fp32 [batch][seq][vocab]); on device buffers it
-        replays a captured graph like a decode step."""
-        flags = (BS_STEP_LOGITS if logits is not None else 0) | (BS_STEP_VERIFY if verify else 0)
+        replays a captured graph like a decode step.
+        draw (with verify): BS_STEP_VERIFY_DRAW -- rows that hold sampler state (set_row_sampler) get their own draw
+        at every position instead of the greedy id; a non-last stage ignores it."""
+        flags = (BS_STEP_LOGITS if logits is not None else 0) | self._verify_flags(verify, draw)
         st, pasts = self._step(batch, seq, slot, past_len, flags)
         _check(self._fwd(self._h, ctypes.byref(st), _ptr(inp), _ptr(out), _ptr(logits), stream))
         if pasts is None:
@@ -384,6 +396,13 @@ class Stage:
         _check(lib().bs_read_row_draw(self._h, int(slot), ctypes.byref(d)))
         return {name: getattr(d, name) for name, _ in RowDraw._fields_}
 
+    def read_verify_draw(self, slot, t):
+        """bs_read_verify_draw: read_row_draw's dict for position `t` of KV row `slot` in the stage's last verify
+        pass with draw=True that ran the sampler.  Synchronises."""
+        d = RowDraw()
+        _check(lib().bs_read_verify_draw(self._h, int(slot), int(t), ctypes.byref(d)))
+        return {name: getattr(d, name) for name, _ in RowDraw._fields_}
+
     def set_graphs(self, on=True):
         """bs_set_graphs: replay captured decode graphs (default) or launch every step eagerly."""
         _check(lib().bs_set_graphs(self._h, 1 if on else 0))
@@ -419,8 +438,9 @@ class Stage:
         _check(lib().bs_head_slice(self._h, _ptr(xn), batch, _ptr(keys_in), _ptr(keys_out), _ptr(tokens), stream))
 
     # ---- host I/O convenience (numpy in, numpy out)
-    def forward_host(self, x, batch, seq, slot=0, past_len=None, want_logits=False, verify=False):
-        """verify: a BS_STEP_VERIFY pass; the last stage returns ids [batch][seq] (and logits [batch][seq][vocab])."""
+    def forward_host(self, x, batch, seq, slot=0, past_len=None, want_logits=False, verify=False, draw=False):
+        """verify: a BS_STEP_VERIFY pass; the last stage returns ids [batch][seq] (and logits [batch][seq][vocab]).
+        draw (with verify): BS_STEP_VERIFY_DRAW, the ids of rows with sampler state are their draws."""
         if self.is_first:
             x = np.ascontiguousarray(x, dtype=np.int32).reshape(batch, seq)
         else:
@@ -428,7 +448,7 @@ class Stage:
         rows = (batch, seq) if verify else (batch,)
         out = np.empty(rows, np.int32) if self.is_last else np.empty((batch, seq, self.hidden), np.float32)
         logits = np.empty(rows + (self.n_out,), np.float32) if want_logits else None
-        flags = BS_STEP_HOST_IO | (BS_STEP_LOGITS if want_logits else 0) | (BS_STEP_VERIFY if verify else 0)
+        flags = BS_STEP_HOST_IO | (BS_STEP_LOGITS if want_logits else 0) | self._verify_flags(verify, draw)
         st, pasts = self._step(batch, seq, slot, past_len, flags)
         _check(lib().bs_forward(self._h, ctypes.byref(st), x.ctypes.data, out.ctypes.data,
                                 logits.ctypes.data if logits is not None else None, None))

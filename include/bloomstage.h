@@ -181,6 +181,31 @@ typedef struct bs_step {
  *   BS_ERR_UNSUPPORTED on a BS_FLAG_INT8_KV stage; BS_ERR_STATE on a classifier stage, after bs_set_sampling chose
  *   top_k > 1, and on a last stage without the whole lm_head.  bs_forward_score rejects the flag (BS_ERR_INVALID). */
 #define BS_STEP_VERIFY 4
+/* step->flags.  BS_STEP_VERIFY_DRAW (only together with BS_STEP_VERIFY, else BS_ERR_INVALID; bs_forward_score rejects
+ * it with BS_ERR_INVALID): the verify step of SAMPLED speculative decoding.  A draw of the per-row sampler depends on
+ * (seed, position, logits) only, so the pass draws the row's own token at every position and the caller keeps the
+ * prefix of its draft that agrees, as with greedy ids: every emitted token is the target's own draw, and the output
+ * distribution is plain sampling's.
+ *   A non-last stage accepts the flag and ignores it (a chain passes one set of flags to every stage).  On the last
+ *   stage, out entry (b, t) of [B][S] is the row sampler's draw (bs_set_row_sampler's rule) on the fp32 logits of
+ *   position past_b + t -- the values BS_STEP_LOGITS returns for it -- with the state of KV row slot + b at draw
+ *   position past_b + t + 1, the index of the token being generated: what a plain seq == 1 step fed at past_b + t
+ *   draws.  Rows of the call without state get the first index of their largest logit at every position.  A call
+ *   none of whose rows holds state is the unflagged verify pass bit for bit (the argmax tail, not the sampler).
+ *   The pass appends S positions; its last kernel (the sampler's pick) advances the device copy of each of the B
+ *   rows' positions by S exactly once.  Rolling back, capture and replay are BS_STEP_VERIFY's: the launches and grids
+ *   are a static function of (B, S, vocab), no launch argument is a per-call host value, and a bs_set_row_sampler
+ *   between two replays takes effect without a recapture.  The pass works in sampler scratch of its own, one lane
+ *   per position: the per-row scratch of plain sampled steps and bs_read_row_draw's read-outs are untouched.
+ *   Every other condition is BS_STEP_VERIFY's: the shape limits, BS_ERR_UNSUPPORTED on an int8 KV cache, BS_ERR_STATE
+ *   on a classifier, without the whole lm_head and after bs_set_sampling chose top_k > 1.  BS_STEP_VERIFY without
+ *   this flag on a row with state stays BS_ERR_STATE.
+ *   Workspace (counted under workspace_bytes from then on): the first pass that runs the sampler allocates the
+ *   per-position scratch for 32 positions (max key, the six count and three mass histograms, launch-to-launch
+ *   states, read-outs, positions; about 3 MB); the first such pass that is given no logits buffer allocates fp32
+ *   logits of max(max_batch, 32) x vocab (a pass with BS_STEP_LOGITS writes and reads the caller's buffer, or with
+ *   BS_STEP_HOST_IO the logits staging). */
+#define BS_STEP_VERIFY_DRAW 8
 
 /* Create a stage on desc->device: allocates weights, KV cache and workspace in HBM. */
 int bs_init_stage(const bs_stage_desc *desc, bs_stage **out);
@@ -315,7 +340,7 @@ typedef struct bs_row_draw {
  * BS_ERR_INVALID: top_k < 0, top_p outside (0, 1], temperature <= 0, infinite or NaN, a bad row range.
  * BS_ERR_UNSUPPORTED: a classifier, a non-last stage, or a stage without the whole lm_head.  BS_ERR_STATE: setting a
  * state while bs_set_sampling holds top_k > 1 (and bs_set_sampling(top_k > 1) while a row holds state; BS_STEP_VERIFY
- * on a row with state).  The first call allocates the table, the selection histograms, the read-outs and, if absent,
+ * without BS_STEP_VERIFY_DRAW on a row with state).  The first call allocates the table, the selection histograms, the read-outs and, if absent,
  * the [max_batch][vocab] logits buffer, counted under workspace_bytes from then on. */
 int bs_set_row_sampler(bs_stage *stage, int32_t slot, int32_t count, const bs_row_sampler *params, void *stream);
 /* Run the row sampler -- the kernels the tail runs -- on caller-given fp32 logits [batch][ld] (ld >= vocab; device, or
@@ -327,6 +352,11 @@ int bs_sample_logits(bs_stage *stage, int32_t slot, int32_t batch, const int32_t
 /* Read-out of row `slot`'s last draw, for verification (synchronises the device), like bs_read_head_screen.
  * BS_ERR_STATE on a stage that never ran the row sampler. */
 int bs_read_row_draw(bs_stage *stage, int32_t slot, bs_row_draw *out);
+/* Read-out of position t (0 <= t < seq) of KV row `slot` in the stage's last BS_STEP_VERIFY_DRAW pass that ran the
+ * sampler (synchronises the device).  A row without state reads as bs_read_row_draw describes.  BS_ERR_STATE if no
+ * such pass ever ran; BS_ERR_INVALID if the row or t was not part of the last one.  bs_read_row_draw keeps its
+ * meaning: the row's last plain draw. */
+int bs_read_verify_draw(bs_stage *stage, int32_t slot, int32_t t, bs_row_draw *out);
 
 /* Decode steps (S = 1) and BS_STEP_VERIFY passes on device buffers are captured once per shape into a hipGraph and replayed
  * (the default, on = 1); on = 0 launches them eagerly every step (same kernels, same results: for
