@@ -139,6 +139,16 @@ void launch_kv_dequant(const void* k_codes, const void* v_codes, const KvQ8& kq,
 void launch_kv_quant(void* k_codes, void* v_codes, const KvQ8& kq, const int* past_dev, int B, int S, int slot,
                      int n_head, int head_dim, int max_ctx, int lmax, hipStream_t s);
 
+// ---- KV row fork (bs_fork_kv; kv_fork.hip) ----
+// Copy the first npos positions of cache row src_slot to rows [dst_slot, dst_slot + count) in one launch: `base` holds
+// n_lw = layers * 2 images [max_batch][n_head][max_ctx] of pos_bytes each (the codes or values of the whole stage, or
+// the fp32 scales of an int8 cache with pos_bytes = 4); every source chunk of chunk_bytes (16, or 4 for the scales;
+// it divides npos * pos_bytes and the alignment of every segment start) is loaded once and stored count times.  Grid:
+// one block per 1024 chunks, at most 8 per CU (cus), grid-stride beyond.  The row ranges must not overlap.
+bool kv_fork_supported(int npos, size_t pos_bytes);
+void launch_kv_fork(void* base, int chunk_bytes, int n_lw, int n_head, int max_batch, int max_ctx, size_t pos_bytes,
+                    int src_slot, int dst_slot, int count, int npos, int cus, hipStream_t s);
+
 // Split-attention partials as the consumer reads them (attn_merge.h).
 struct AttnParts {
   const float* acc;  // AttnArgs::part_acc

@@ -939,6 +939,34 @@ extern "C" int bs_reset_kv(bs_stage* s, int32_t slot) {
   return BS_OK;
 }
 
+// KV row fork (kv_fork.hip): one launch for the codes or values of every layer, one more for an int8 cache's scales.
+// Enqueues only: no allocation, no synchronisation, no host copy, and the captured graphs stay (a graph's key holds
+// no cache content).  past_dev / past_next are indexed by a call's rows and re-written by the next forward whose
+// past_lens differ, so they need no update here.
+extern "C" int bs_fork_kv(bs_stage* s, int32_t src_slot, int32_t dst_slot, int32_t count, int32_t npos, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  const int mb = s->d.max_batch;
+  if (src_slot < 0 || dst_slot < 0 || count < 0 || npos < 0) return fail(BS_ERR_INVALID, "negative slot, count or npos");
+  if (src_slot >= mb || dst_slot > mb - count) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (npos > s->d.max_ctx) return fail(BS_ERR_INVALID, "npos beyond max_ctx");
+  if (src_slot >= dst_slot && src_slot - dst_slot < count) return fail(BS_ERR_INVALID, "the source row is one of the destination rows");
+  if (!count || !npos || s->L <= 0) return BS_OK;
+  const size_t pos_bytes = (size_t)s->hd * (s->kv8 ? 1 : s->esz);  // a multiple of 16 (head_dim % 8, % 16 for int8)
+  if (!kv_fork_supported(npos, pos_bytes)) return fail(BS_ERR_UNSUPPORTED, "npos * head_dim too large for the fork kernel");
+  HIP_TRY(hipSetDevice(s->d.device));
+  if (s->cus <= 0 && hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, s->d.device) != hipSuccess) {
+    (void)hipGetLastError();
+    s->cus = 0;  // the launch falls back to 256
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  launch_kv_fork(s->kv, 16, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, pos_bytes, src_slot, dst_slot, count, npos, s->cus, st);
+  if (s->kv8)  // scale segments start on 4-byte boundaries only
+    launch_kv_fork(s->kv_scales, 4, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, 4, src_slot, dst_slot, count, npos, s->cus, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kv fork: ") + hipGetErrorString(err));
+  return BS_OK;
+}
+
 // ---- profiling
 extern "C" int bs_profile_enable(bs_stage* s, int32_t cls) {
   if (!s) return fail(BS_ERR_INVALID, "stage is NULL");

@@ -100,6 +100,15 @@ class StageExecutor:
             return
         self._run(call, ())
 
+    def fork_kv(self, src, dst, npos, count=1):
+        """Stage.fork_kv: positions [0, npos) of KV row `src` copied to rows [dst, dst + count), ordered like
+        forward."""
+        sh = self._sh if self._sh is not None else torch.cuda.current_stream().cuda_stream
+        if sh:
+            self.stage.fork_kv(src, dst, npos, count=count, stream=sh)
+            return
+        self._run(lambda h: self.stage.fork_kv(src, dst, npos, count=count, stream=h), ())
+
     def head_norm(self, hidden, batch, seq, xn):
         sh = torch.cuda.current_stream().cuda_stream
         if sh:
@@ -308,14 +317,28 @@ class Pipeline:
             # stream up again, so its forward stays ordered with its own receive and send
             self.ex.set_stream(None)
 
-    def prefill_row(self, j, r, ids, n):
-        """One pipeline pass of row r of micro-batch j alone: its n prompt tokens at positions 0..n-1 of KV slot
-        j * mb + r (a new sample taking the row: serve.py's admission prefill, Communication.java:418-464).
-        `ids` int32 [1, n] on rank 0 (None elsewhere).  The first generated token lands in self.pf_tok[j][r] on
-        rank 0 (stream-ordered); it travels on `pf_group`, so it never interleaves with the decode rounds'
-        token returns on `tok_group`.  Every rank calls this in the same order as every other rank."""
+    @property
+    def template_slot(self):
+        """The first KV row after the pool's rows (build_rank(..., extra_rows >= 1)): the shared-prefix template."""
+        return self.mb * self.n_mb
+
+    def fork_row(self, src_slot, j, r, npos):
+        """Copy cached positions [0, npos) of KV row `src_slot` (e.g. template_slot) into row r of micro-batch j, on
+        every rank inside its own stage (bs_fork_kv), ordered with the rank's forwards on its current stream.  No
+        communication; every rank calls this in the same order as every other rank."""
+        self.ex.fork_kv(src_slot, j * self.mb + r, npos)
+
+    def prefill_row(self, j, r, ids, n, past=0, slot=None):
+        """One pipeline pass of row r of micro-batch j alone: its n prompt tokens at positions past..past+n-1 of KV
+        slot j * mb + r (a new sample taking the row: serve.py's admission prefill, Communication.java:418-464;
+        past > 0: the rest of a prompt whose first `past` positions the row already holds, e.g. after fork_row).
+        `slot` (None: j * mb + r) names another KV row, e.g. template_slot; the pass still uses the buffers of
+        (j, r).  `ids` int32 [1, n] on rank 0 (None elsewhere).  The first generated token lands in
+        self.pf_tok[j][r] on rank 0 (stream-ordered); it travels on `pf_group`, so it never interleaves with the
+        decode rounds' token returns on `tok_group`.  Every rank calls this in the same order as every other rank."""
         n_el = n * self.h
-        slot = j * self.mb + r
+        if slot is None:
+            slot = j * self.mb + r
         tok = self.pf_tok[j][r:r + 1]
         self._drain(self.pending[j])
         if self.is_first:
@@ -324,12 +347,12 @@ class Pipeline:
             inp = self.hin[j][:n_el]
             _recv(inp, self.rank - 1)
         if self.is_last and not self.head_split:
-            self.ex.forward(inp, tok, 1, n, slot, 0)
+            self.ex.forward(inp, tok, 1, n, slot, past)
             if self.world > 1:
                 self.pending[j].append(dist.isend(tok, dst=0, group=self.pf_group))
         else:
             out = self.hout[j][:n_el]
-            self.ex.forward(inp, out, 1, n, slot, 0)
+            self.ex.forward(inp, out, 1, n, slot, past)
             if not self.is_last:
                 self.pending[j].append(dist.isend(out, dst=self.rank + 1))
             else:  # head_split: open the head ring
@@ -537,12 +560,15 @@ def connect_p2p(rank, world, head_split, groups, device):
 
 
 def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb_rows=1, n_mb=None, max_ctx=1024,
-               max_seq=512, seed=0, head_split=None, executor_factory=None, n_labels=0, kv_int8=False, sample=False):
+               max_seq=512, seed=0, head_split=None, executor_factory=None, n_labels=0, kv_int8=False, sample=False,
+               extra_rows=0):
     """Create this rank's stage (server.py:893-905 layer range, plus a vocabulary slice of the
     tied lm_head when head_split) and its Pipeline.  n_labels > 0: the last stage is a sequence-classification
     tail (BS_FLAG_CLASSIFIER; `classify` runs the task) and there is no head ring.  kv_int8: every stage keeps an
     int8 KV cache (BS_FLAG_INT8_KV; bf16 stages of the HIP library only).  sample: the run samples per row
     (Pipeline.set_row_sampler), which needs the whole lm_head on the last stage, as `score` does: no head ring.
+    extra_rows: KV rows of the stage beyond the pool's mb_rows * n_mb (max_batch = mb_rows * n_mb + extra_rows); the
+    first of them is Pipeline.template_slot, the shared-prefix template that fork_row copies from.
     Collective: every rank must call it."""
     if sample:
         if n_labels:
@@ -575,14 +601,15 @@ def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb
     if executor_factory is None:
         from .stage import Stage
         st = Stage(model.hidden, model.n_head, model.n_layer, model.vocab, lb, le, dtype=dtype,
-                   device=device.index if device.type == "cuda" else 0, max_batch=mb_rows * n_mb,
+                   device=device.index if device.type == "cuda" else 0, max_batch=mb_rows * n_mb + extra_rows,
                    max_ctx=max_ctx, max_tokens=mb_rows * max_seq, seed=seed, is_first=is_first,
                    is_last=is_last and not head_split, head_slice=hslice, int8_weights=model.int8_weights,
                    n_labels=n_labels if is_last else 0, kv_int8=kv_int8, mxfp4_weights=model.mxfp4_weights)
         ex = StageExecutor(st)
     else:
         kw = {"n_labels": n_labels} if (n_labels and is_last) else {}
-        ex = executor_factory(lb, le, is_first, is_last and not head_split, mb_rows * n_mb, max_ctx, hslice, **kw)
+        ex = executor_factory(lb, le, is_first, is_last and not head_split, mb_rows * n_mb + extra_rows, max_ctx, hslice,
+                              **kw)
     # communicators are created collectively, in the same order on every rank
     tok_group = head_group = pf_group = None
     if world > 1:

@@ -45,6 +45,11 @@ stage (no head ring).
 state set before each sample's prefill and verify passes that return the row's own draw at every position
 (BS_STEP_VERIFY_DRAW).  The tokens are plain sampled decoding's for the same state and seed; a draft model holds the
 same state, so it draws with the target's u at every position.
+--shared-prefix P: the first P tokens of every prompt are the same (a system prompt, few-shot examples) and are
+prefilled once, into a template KV row behind the pool's rows; an admitted sample forks the template into its row
+(bs_fork_kv, a device copy of the P cached positions on every rank) and prefills only the rest of its prompt at
+past = P.  The schedule is unchanged.  --prefix-fork 0 is the A/B baseline: every sample prefills the prefix in its own
+row with a pass of the same shape, then the rest, so both settings return the same tokens.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
 unseeded top-k, token ids in (no tokenizer).
@@ -93,8 +98,16 @@ class RunConfig:
     temperature: float = 1.0      # sampling: > 0
     sample_seed: int = 0          # sampling: sample i draws with request_seed(sample_seed, i)
     sample_speculate: int = 0     # sampled speculative decoding: tokens drafted per verify-draw pass (0 = off; needs sample)
+    shared_prefix: int = 0        # the first shared_prefix tokens of every prompt are identical and are prefilled once
+    prefix_fork: bool = True      # shared_prefix: fork the template row (else every sample prefills the prefix itself)
 
     def __post_init__(self):
+        if self.shared_prefix < 0:
+            raise ValueError(f"shared_prefix must be >= 0 (got {self.shared_prefix})")
+        if self.shared_prefix:
+            if (not self.prefill or self.score or self.max_length <= 0 or self.speculate or self.sample_speculate):
+                raise ValueError("shared_prefix is plain generation with admission prefills: it excludes "
+                                 "prefill = False, score, max_length == 0, speculate and sample_speculate")
         if self.kv not in ("bf16", "int8"):
             raise ValueError(f"kv must be 'bf16' or 'int8' (got {self.kv!r})")
         if self.speculate:
@@ -137,8 +150,13 @@ def request_seed(sample_seed, i):
 
 
 def synthetic_prompts(cfg: RunConfig, vocab):
+    """shared_prefix: every sample begins with prompt 0's first shared_prefix tokens."""
     from .stage import prompt_ids
-    return [prompt_ids(1234 + i, 1, cfg.prompt_len, vocab).reshape(-1).tolist() for i in range(cfg.num_sample)]
+    P = cfg.shared_prefix
+    if P and cfg.prompt_len <= P:
+        raise ValueError(f"prompt_len ({cfg.prompt_len}) must exceed shared_prefix ({P}): a token of its own per sample")
+    out = [prompt_ids(1234 + i, 1, cfg.prompt_len, vocab).reshape(-1).tolist() for i in range(cfg.num_sample)]
+    return [out[0][:P] + p[P:] for p in out] if P else out
 
 
 def admission_schedule(lens, max_length, rows, prefill=True):
@@ -184,12 +202,22 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
         lens = [len(p) for p in prompts]
     else:
         lens = [0] * cfg.num_sample
+    P = cfg.shared_prefix
+    if P:  # rank 0's verdict on the prefixes travels behind the lengths, so every rank raises together
+        lens.append(int(rank == 0 and any(p[:P] != prompts[0][:P] for p in prompts if len(p) > P)))
     if world > 1:  # the prompt lengths travel with the config (server -> devices)
         t = torch.tensor(lens, dtype=torch.int64)
         if dist.get_backend() == "nccl":
             t = t.to(device)
         dist.broadcast(t, src=0)
         lens = [int(v) for v in t.tolist()]
+    if P:
+        differ = lens.pop()
+        if min(lens) <= P:
+            raise ValueError(f"shared_prefix = {P}: every prompt must be longer (shortest: {min(lens)}); the "
+                             "continuation pass needs a token")
+        if differ:
+            raise ValueError(f"shared_prefix = {P}: the prompts' first {P} tokens differ")
     if cfg.score:
         return _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.max_length == 0:
@@ -202,6 +230,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     mb = -(-cfg.core_pool_size // n_mb)
     rows = n_mb * mb
     pf = cfg.prefill
+    fork = bool(P) and cfg.prefix_fork  # the prefix is prefilled once into a template row and forked at admission
     sched, T = admission_schedule(lens, cfg.max_length, rows, prefill=pf)
     # per decode round and row: position, and (rank 0) the fed token / whether it overrides the returned one;
     # with prefill, `take_pf` marks a sample's first decode round, whose input is its prefill's token
@@ -229,9 +258,10 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + cfg.max_length + 1, max_seq=max_seq, seed=cfg.seed,
                                 head_split=cfg.head_split, executor_factory=executor_factory,
-                                kv_int8=cfg.kv == "int8", sample=cfg.sample)
+                                kv_int8=cfg.kv == "int8", sample=cfg.sample, extra_rows=int(fork))
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
-                    "micro_batches": n_mb, "rows_per_micro_batch": mb, "rounds": T, "prefill": pf})
+                    "micro_batches": n_mb, "rows_per_micro_batch": mb, "rounds": T, "prefill": pf,
+                    **({"shared_prefix": P, "prefix_fork": fork} if P else {})})
     sampling = ({"top_k": cfg.top_k, "top_p": cfg.top_p, "temperature": cfg.temperature} if cfg.sample else None)
     cuda = device.type == "cuda"
     if cuda:
@@ -242,6 +272,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     tp = torch.tensor(take_pf or [[False] * rows], dtype=torch.bool, device=device).view(shape)
     pids = ([torch.tensor(p, dtype=torch.int32, device=device).view(1, -1) for p in prompts]
             if (pf and rank == 0) else None)
+    # shared_prefix: each prompt as (prefix, rest) views (rank 0)
+    pre = [p[:, :P] if pids is not None else None for p in (pids or [None] * cfg.num_sample)] if P else None
+    rest = [p[:, P:] if pids is not None else None for p in (pids or [None] * cfg.num_sample)] if P else None
     if world > 1:
         dist.barrier()
     # ---- run (Running)
@@ -249,12 +282,26 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     rec = [[] for _ in range(n_mb)] if pipe.is_first else None
     first = [None] * cfg.num_sample  # prefill: each sample's first generated token (rank 0)
     pipe.tokens_held = True  # round 0 feeds every row
+    prefill_tokens = 0
     t_start = time.perf_counter()
+    if fork:  # the template: one ordinary prefill pass of the shared prefix into the row after the pool's; its
+        # token is discarded and the row never holds sampler state
+        pipe.prefill_row(0, 0, pre[0], P, slot=pipe.template_slot)
+        prefill_tokens += P
     for t in range(T + 1):
         for i, r in admit[t] if pf else ():
             if sampling:  # the row's sampler for this request, ordered before its prefill pass (last rank)
                 pipe.set_row_sampler(r // mb, r % mb, seed=request_seed(cfg.sample_seed, i), **sampling)
-            tok = pipe.prefill_row(r // mb, r % mb, pids[i] if pids is not None else None, lens[i])
+            if fork:
+                pipe.fork_row(pipe.template_slot, r // mb, r % mb, P)
+            elif P:  # the A/B baseline: a pass of the template's shape computes the prefix in the row itself
+                pipe.prefill_row(r // mb, r % mb, pre[i], P)
+                prefill_tokens += P
+            if P:  # the rest of the prompt behind the prefix; its tail yields the first generated token
+                tok = pipe.prefill_row(r // mb, r % mb, rest[i], lens[i] - P, past=P)
+            else:
+                tok = pipe.prefill_row(r // mb, r % mb, pids[i] if pids is not None else None, lens[i])
+            prefill_tokens += lens[i] - P
             if rank == 0:
                 first[i] = tok.clone()
         if t == T:
@@ -286,6 +333,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
            "prefill": pf, "seconds": dt, "tokens_per_s": cfg.num_sample * cfg.max_length / dt}
     if sampling:
         res.update(sample=True, sample_seed=cfg.sample_seed, **sampling)
+    if P:  # prefill_tokens: the tokens pushed through prefill passes, the template's included
+        res.update(shared_prefix=P, prefix_fork=fork, prefill_tokens=prefill_tokens)
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
     say(STATES[3], {})
     return res

@@ -104,7 +104,7 @@ EXPORTS = [
     "bs_build_id", "bs_hbm_probe", "bs_mfma_probe", "bs_init_stage_file", "bs_weights_file_probe",
     "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
     "bs_forward_score", "bs_set_row_sampler", "bs_sample_logits", "bs_read_row_draw",
-    "bs_read_verify_draw",
+    "bs_read_verify_draw", "bs_fork_kv",
 ]
 
 _LIB = None
@@ -134,6 +134,7 @@ def lib():
         L.bs_forward_score.argtypes = [vp, ctypes.POINTER(Step), vp, vp, vp, vp, vp]
         L.bs_reset_kv.argtypes = [vp, i32]
         L.bs_read_kv.argtypes = [vp, i32, i32, i32, i32, vp]
+        L.bs_fork_kv.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bs_release.argtypes = [vp]
         L.bs_release.restype = None
         L.bs_last_error.restype = ctypes.c_char_p
@@ -473,6 +474,15 @@ class Stage:
             self.past = [0] * self.max_batch
         else:
             self.past[slot] = 0
+
+    def fork_kv(self, src, dst, npos=None, count=1, stream=None):
+        """bs_fork_kv: copy cached positions [0, npos) of KV row `src` to rows [dst, dst + count), every layer of the
+        stage (npos None: all the positions the host mirror holds for `src`).  Stream ordered like forward(); the
+        forked rows then stand at npos.  Sampler state is per row and is not copied."""
+        if npos is None:
+            npos = self.past[src]
+        _check(lib().bs_fork_kv(self._h, int(src), int(dst), int(count), int(npos), stream))
+        self.past[dst:dst + count] = [int(npos)] * count
 
     def read_kv(self, layer, slot, pos0, npos):
         """KV row `slot` of local layer `layer`, positions [pos0, pos0+npos): fp32 [2 (K, V)][n_head][npos][hd]."""

@@ -12,6 +12,7 @@
  *                         runInferenceWorkerResidualLastGeneration (:1368-1443, tail stage),
  *                         all of which end in inference::run_inference (inference.cpp:145-218)
  *   bs_reset_kv        <- (none: the reference has no KV cache; new sample == new slot)
+ *   bs_fork_kv         <- (none: no KV cache, so no shared prompt prefix to reuse)
  *   bs_forward_score   <- (none: the reference has no scoring task)
  *   bs_last_error      <- (none: the reference throws C++ exceptions across JNI,
  *                         native-lib.cpp:986-988; here errors are status codes + this string)
@@ -387,6 +388,23 @@ int bs_reset_kv(bs_stage *stage, int32_t slot);
  * out[2 (K, V)][n_head][npos][head_dim].  Synchronizes the stage's own stream; the caller orders any
  * other stream it forwarded on.  For verification (parity tests hand a device cache to the checker). */
 int bs_read_kv(const bs_stage *stage, int32_t layer, int32_t slot, int32_t pos0, int32_t npos, float *out);
+/* KV row fork: copy cached positions [0, npos) of KV row src_slot to rows [dst_slot, dst_slot +
+ * count), all layers of the stage, K and V, every head; ordered on `stream` (NULL = the stage's own) like a forward.
+ * A prompt prefix prefilled once into one row serves every row that begins with it: fork, then a continuation
+ * bs_forward (seq > 1 at past_len = npos) of the rest of the row's prompt.
+ *   Ordering: the call enqueues and returns; it does not synchronise, allocates nothing and keeps every captured graph.
+ *   The caller orders it behind the forwards that wrote the source row and ahead of the next forward on the
+ *   destination rows -- the same stream, or an event; one stage is single-producer (bs_forward).  One launch whatever
+ *   the layer count, one more for the scales of a BS_FLAG_INT8_KV cache.
+ *   Exact copy: afterwards positions [0, npos) of every destination row hold the source row's bits -- bf16 or fp32
+ *   elements; on a BS_FLAG_INT8_KV cache the int8 codes and the fp32 scales verbatim, nothing is re-quantised.
+ *   Nothing else is written: positions >= npos of the destination rows, every other row and the source stay as they
+ *   were, as do the bf16 staging of an int8 cache, the device copy of the rows' positions (indexed by a row's place in
+ *   a call, not by slot: the next forward's past_lens says where the rows stand) and the per-row sampler table (a
+ *   forked row keeps the sampler state it had; bs_set_row_sampler sets it).
+ *   BS_OK and no launch for npos == 0, count == 0 or a stage without layers.  BS_ERR_INVALID: a NULL stage, a negative
+ *   slot, count or npos, a slot range outside max_batch, npos > max_ctx, src_slot inside [dst_slot, dst_slot + count). */
+int bs_fork_kv(bs_stage *stage, int32_t src_slot, int32_t dst_slot, int32_t count, int32_t npos, void *stream);
 
 void bs_release(bs_stage *stage);
 
