@@ -6,6 +6,16 @@
 //   releaseSession (native-lib.cpp:1290-1303)                                       -> bs_release
 // Everything the ONNX sub-model computed on the CPU is here a sequence of gfx950 kernels
 // (kernels.hip) over weights, KV cache and workspace resident in the stage GPU's HBM.
+//
+// Sections, in order:
+//   errors and tracing; Carver (one device allocation cut into aligned pieces); bs_stage and the allocations it owns
+//   validate, bs_stage_weight_count (the weight table is stage_weights.h), checkpoint lookup
+//   init_stage: weight arena + binding, the three weight sources, head screening, KV cache, workspace
+//   bs_stage_info, bs_read_weights, bs_read_kv, bs_reset_kv, bs_fork_kv
+//   profiling, bs_stream_delay, the HBM and MFMA probes
+//   the forward: linear / linear_ln, Tail (which tail a pass ends in, decided once), enqueue_forward
+//   head slices, sampling setters, the per-row sampler and verify-draw buffers, the graph cache
+//   forward_impl (checks, lazy buffers, capture or eager enqueue), bs_forward, bs_forward_score
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +30,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "safetensors.h"
+#include "stage_weights.h"
 
 static thread_local std::string g_err;
 
@@ -52,29 +63,42 @@ static int fail(int code, const std::string& msg) {
 
 namespace {
 
-enum { T_LN1_G, T_LN1_B, T_QKV_W, T_QKV_B, T_DENSE_W, T_DENSE_B, T_LN2_G, T_LN2_B, T_FC1_W, T_FC1_B,
-       T_FC2_W, T_FC2_B, T_NLAYER };
-enum { M_WEMB = 0, M_EMB_G = 1, M_EMB_B = 2, M_LNF_G = 3, M_LNF_B = 4, M_SCORE = 5 };
-
 struct Layer {
   void* t[T_NLAYER];
   float* sc[T_NLAYER];  // int8 stages: per-row scales of the four weight matrices (else null)
   uint8_t* mxs[T_NLAYER];  // MXFP4 stages: E8M0 block scales of the four weight matrices (else null); t[] = codes
 };
 
-static bool is_matrix(int t) { return t == T_QKV_W || t == T_DENSE_W || t == T_FC1_W || t == T_FC2_W; }
+// What a pass ends in.  plan_tail decides it once per call from the stage state and the step; enqueue_forward, the
+// graph key, the lazy buffers and the read-out bookkeeping all take it from there.
+enum TailKind {
+  TAIL_NONE,           // not the last stage: hidden states out
+  TAIL_CLASSIFY,       // ln_f of each row's last position, score, first maximal class
+  TAIL_SCORE,          // bs_forward_score: log-softmax head over every position
+  TAIL_VERIFY_ARGMAX,  // BS_STEP_VERIFY: the greedy id of every position
+  TAIL_VERIFY_DRAW,    // BS_STEP_VERIFY_DRAW on rows with sampler state: the row sampler's draw at every position
+  TAIL_SCREENED,       // greedy, <= 2 rows, no logits: int8 screening pass + exact re-score
+  TAIL_GREEDY,         // full head, argmax
+  TAIL_TOPK,           // full head, bs_set_sampling's seeded top-k
+  TAIL_ROWS,           // full head, per-row sampler (a row of the call holds sampler state)
+};
+struct Tail {
+  TailKind kind = TAIL_NONE;
+  int rows = 0;   // ids (and logits rows) the tail writes: batch, or batch * seq for the verify tails
+  int width = 0;  // logits per row: n_labels or vocab
+};
 
 struct GraphKey {
   int B, seq, slot, flags;
-  int rows;  // the tail runs the per-row sampler (a row of the call holds sampler state); with BS_STEP_VERIFY_DRAW
-             // in flags, the verify tail draws at every position
+  TailKind tail;  // row-sampler state changes the tail of otherwise equal calls (the setters that change it for
+                  // every call drop the graphs instead)
   const void* in;
   void* out;
   float* logits;
   hipStream_t st;
   bool operator==(const GraphKey& o) const {
-    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && rows == o.rows && in == o.in && out == o.out && logits == o.logits &&
-           st == o.st;
+    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && tail == o.tail && in == o.in &&
+           out == o.out && logits == o.logits && st == o.st;
   }
 };
 
@@ -106,6 +130,40 @@ static int graphs_default() {
   return (e && e[0] == '0') ? 0 : 1;
 }
 
+static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// One device allocation cut into typed pieces, each 256-B aligned: piece() names where each pointer goes and its
+// size, alloc() allocates once and sets the pointers (none of them on failure).
+struct Carver {
+  std::vector<std::pair<void**, size_t>> pieces;  // (pointer to set, offset)
+  size_t total = 0;
+  char* base = nullptr;
+  template <typename T>
+  void piece(T** p, size_t bytes) {
+    pieces.push_back({(void**)p, total});
+    total = align_up(total + bytes, 256);
+  }
+  enum { OK, NO_MEMORY, NOT_ZEROED };
+  // zero_on (the stage's own stream): the pieces are zeroed there and the stream synchronised before any other stream
+  // can write them (a plain hipMemset of device memory may still be running when it returns, and the caller's
+  // stream is not ordered behind it).  Nothing stays allocated on failure.
+  int alloc(hipStream_t zero_on = nullptr) {
+    if (hipMalloc((void**)&base, total ? total : 256) != hipSuccess) return NO_MEMORY;
+    if (zero_on && (hipMemsetAsync(base, 0, total, zero_on) != hipSuccess || hipStreamSynchronize(zero_on) != hipSuccess)) {
+      hipFree(base);
+      return NOT_ZEROED;
+    }
+    for (auto& p : pieces) *p.first = base + p.second;
+    return OK;
+  }
+};
+
+// A device allocation the stage owns; `counted` is what bs_stage_info reports of it as workspace beside `ws`.
+struct OwnedAlloc {
+  void* p;
+  size_t counted;
+};
+
 struct bs_stage {
   bs_stage_desc d;
   int bf16 = 1;
@@ -117,7 +175,6 @@ struct bs_stage {
   int hd = 0, L = 0;
   hipStream_t own = nullptr;
   // HBM
-  char* wbase = nullptr;
   size_t wbytes = 0;
   void* wemb = nullptr;
   void* emb_g = nullptr;
@@ -164,10 +221,11 @@ struct bs_stage {
   float* sk_ws = nullptr;              // batched-GEMV split-K partials (kSkCap floats)
   unsigned* sk_tickets = nullptr;      // [kSkTickets]
   ProfClass prof;
-  std::vector<std::pair<void*, size_t>> order;  // canonical weight order (BS_WEIGHTS_HOST layout)
-  std::vector<std::pair<const float*, int>> order_q8;  // per order entry: (row scales, K) if int8, else (null, 0)
-  std::vector<std::pair<const uint8_t*, int>> order_mx;  // per order entry: (block scales, K) if MXFP4, else (null, 0)
+  std::vector<WeightEntry> weights;  // weight_table(&d), each entry bound to its place in the arena
   std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;  // captured decode steps
+  // Every device allocation of the stage, made at init or by the first call that needs it; the fields above and below
+  // point into them.  free_stage and bs_stage_info walk this list.
+  std::vector<OwnedAlloc> owned;
   float* logit_buf = nullptr;       // host-I/O logits staging
   size_t logit_cap = 0;
   // tail token pick (bs_set_sampling): top_k <= 1 greedy, else seeded top-k sampling
@@ -180,42 +238,32 @@ struct bs_stage {
   // kernels)
   int graphs_on = graphs_default();
   // greedy lm_head screening (kernels.hip "Greedy lm_head screening"): the int8 shadow copy of the tied embedding,
-  // its bound constants and the per-step buffers, one allocation made at init (null: none, screening stays off)
-  char* hs_base = nullptr;
-  size_t hs_bytes = 0;
+  // its bound constants and the per-step buffers, one allocation made at init (hs.Q null: none, screening stays off)
   HeadScreen hs{};
   int hs_on = 0;         // bs_set_head_screen; starts on where the shadow copy exists (and BS_HEAD_SCREEN is not 0)
   int hs_last_rows = 0;  // rows of the last forward if its tail ran screened, else 0 (bs_read_head_screen)
   int cus = 0;           // CUs of the device (grids of the screened tail and of the scoring head)
   // bs_forward_score (head_score.hip): the per-split partials of the scoring head and the host-I/O staging of
-  // targets / top_ids / scores, one allocation made by the first scoring call (null: the stage never scored)
-  char* sc_base = nullptr;
-  size_t sc_bytes = 0;
+  // targets / top_ids / scores, one allocation made by the first scoring call (sc_parts null: the stage never scored)
   void* sc_parts = nullptr;
   int* sc_targets = nullptr;  // [max_tokens]
   int* sc_top = nullptr;      // [max_tokens]
   float* sc_scores = nullptr; // [max_tokens][3]
   // BS_STEP_VERIFY (attn_verify.hip): the short-query attention's split partials for kVerifyMaxTokens positions, the
-  // tail's argmax keys and ids of every position, one allocation made by the first verify call (null: never verified)
-  char* vf_base = nullptr;
-  size_t vf_bytes = 0;
+  // tail's argmax keys and ids of every position, one allocation made by the first verify call (vf_acc null: never)
   float* vf_acc = nullptr;             // [kVerifyMaxTokens][n_head][vf_stride][hd]
   float* vf_ml = nullptr;              // [kVerifyMaxTokens][n_head][vf_stride][2]
   int vf_stride = 0;                   // attention_verify_split_stride
   unsigned long long* vf_keys = nullptr;  // [kVerifyMaxTokens][V/16] (last stage)
   int* vf_tok = nullptr;               // [kVerifyMaxTokens] host-I/O staging of the ids
   // per-row sampling (row_sample.hip): the device table, histograms and read-outs, one allocation made by the first
-  // bs_set_row_sampler / bs_sample_logits (null: never used); rs_host mirrors the table for routing
-  char* rs_base = nullptr;
-  size_t rs_bytes = 0;                 // rs_base, plus sample_logits when that call allocated it
+  // bs_set_row_sampler / bs_sample_logits (rs.table null: never used); rs_host mirrors the table for routing
   RowSampleBufs rs{};
   std::vector<RowSamplerDev> rs_host;  // [max_batch]
   int rs_active = 0;                   // rows that hold state
-  // BS_STEP_VERIFY_DRAW: the sampler scratch of kVerifyMaxTokens positions (vd_base, made by the first verify-draw
-  // pass that runs the sampler) and the [max(max_batch, kVerifyMaxTokens)][V] logits its tail reads when the caller
+  // BS_STEP_VERIFY_DRAW: the sampler scratch of kVerifyMaxTokens positions (vd, made by the first verify-draw pass
+  // that runs the sampler) and the [max(max_batch, kVerifyMaxTokens)][V] logits its tail reads when the caller
   // gives no device logits (vd_logits, made by the first such pass); vd_last_*: the shape of the last such pass
-  char* vd_base = nullptr;
-  size_t vd_bytes = 0;                 // vd_base and vd_logits
   RowSampleBufs vd{};
   float* vd_logits = nullptr;
   int vd_last_slot = 0, vd_last_B = 0, vd_last_S = 0;  // B == 0: no verify-draw pass ran
@@ -228,28 +276,14 @@ struct ScoreIO {
   float* scores;
 };
 
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-static uint64_t host_sm64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-static uint64_t tensor_key(uint64_t seed, int layer, uint32_t tid) {
-  return host_sm64(seed ^ host_sm64(((uint64_t)(uint32_t)(layer + 1) << 8) | tid));
-}
-static int layer_kind(int tid) {
-  switch (tid) {
-    case T_LN1_G: case T_LN2_G: return 2;
-    case T_LN1_B: case T_LN2_B: return 3;
-    case T_QKV_W: case T_DENSE_W: case T_FC1_W: case T_FC2_W: return 0;
-    default: return 1;
+// Allocate `bytes` into the list the stage owns (freed with the stage), counted as workspace or not.
+static bool owned_alloc(bs_stage* s, size_t bytes, bool counted, void** out) {
+  if (hipMalloc(out, bytes) != hipSuccess) {
+    *out = nullptr;
+    return false;
   }
-}
-static void layer_sizes(size_t h, size_t* sz) {
-  const size_t s[T_NLAYER] = {h, h, 3 * h * h, 3 * h, h * h, h, h, h, 4 * h * h, 4 * h, 4 * h * h, h};
-  for (int i = 0; i < T_NLAYER; i++) sz[i] = s[i];
+  s->owned.push_back({*out, counted ? bytes : 0});
+  return true;
 }
 
 // ALiBi slopes, build_alibi_tensor (modeling_bloom.py:60-78).
@@ -299,7 +333,7 @@ static int validate(const bs_stage_desc* d, bool from_file = false) {
   if (d->flags & BS_FLAG_CLASSIFIER) {
     if (!d->is_last) return fail(BS_ERR_INVALID, "BS_FLAG_CLASSIFIER needs the last stage");
     if (d->n_labels < 1 || d->n_labels > 64) return fail(BS_ERR_INVALID, "n_labels must be in [1, 64]");
-    if (d->head_vocab_end > d->head_vocab_begin) return fail(BS_ERR_INVALID, "a classifier stage takes no head slice");
+    if (has_head_slice(d)) return fail(BS_ERR_INVALID, "a classifier stage takes no head slice");
   }
   if ((d->flags & BS_FLAG_INT8_WEIGHTS) && d->dtype != BS_DT_BFLOAT16)
     return fail(BS_ERR_UNSUPPORTED, "BS_FLAG_INT8_WEIGHTS needs dtype BFLOAT16");
@@ -308,17 +342,8 @@ static int validate(const bs_stage_desc* d, bool from_file = false) {
 
 extern "C" uint64_t bs_stage_weight_count(const bs_stage_desc* d) {
   if (validate(d) != BS_OK) return 0;
-  const uint64_t h = (uint64_t)d->hidden;
   uint64_t n = 0;
-  const bool cls = (d->flags & BS_FLAG_CLASSIFIER) != 0;
-  if (d->is_first || (d->is_last && !cls)) n += (uint64_t)d->vocab * h;
-  if (d->is_first) n += 2 * h;
-  n += (uint64_t)(d->layer_end - d->layer_begin) * (12 * h * h + 13 * h);
-  if (d->is_last) n += 2 * h;
-  if (cls) n += (uint64_t)d->n_labels * h;
-  const bool slice = d->head_vocab_end > d->head_vocab_begin;
-  if (slice && !d->is_first && !d->is_last) n += (uint64_t)(d->head_vocab_end - d->head_vocab_begin) * h;
-  if (slice && !d->is_last) n += 2 * h;
+  for (const WeightEntry& w : weight_table(d)) n += w.count;
   return n;
 }
 
@@ -349,56 +374,13 @@ static void free_stage(bs_stage* s) {
   if (s->own) hipStreamSynchronize(s->own);
   for (auto e : s->prof.ev) hipEventDestroy(e);
   for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
-  if (s->wbase) hipFree(s->wbase);
-  if (s->kv) hipFree(s->kv);
-  if (s->kv_stage) hipFree(s->kv_stage);
-  if (s->ws) hipFree(s->ws);
-  if (s->logit_buf) hipFree(s->logit_buf);
-  if (s->sample_logits) hipFree(s->sample_logits);
-  if (s->wtmp) hipFree(s->wtmp);
-  if (s->hs_base) hipFree(s->hs_base);
-  if (s->sc_base) hipFree(s->sc_base);
-  if (s->vf_base) hipFree(s->vf_base);
-  if (s->rs_base) hipFree(s->rs_base);
-  if (s->vd_base) hipFree(s->vd_base);
-  if (s->vd_logits) hipFree(s->vd_logits);
+  for (const OwnedAlloc& a : s->owned) hipFree(a.p);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
 
-// Checkpoint tensor of each canonical-order entry (the BS_WEIGHTS_HOST layout), HF BloomModel names
-// (modeling_bloom.py; the names the reference's ONNX modules were exported from).
-struct FileEntry {
-  std::string name;
-  uint64_t first;                // element offset inside the checkpoint tensor (head slice rows)
-  std::vector<int64_t> shape;    // the checkpoint tensor's expected shape
-};
-static std::vector<FileEntry> file_entries(const bs_stage_desc* d) {
-  const int64_t h = d->hidden, V = d->vocab;
-  std::vector<FileEntry> e;
-  const bool cls = (d->flags & BS_FLAG_CLASSIFIER) != 0;
-  if (d->is_first || (d->is_last && !cls)) e.push_back({"word_embeddings.weight", 0, {V, h}});
-  if (d->is_first) {
-    e.push_back({"word_embeddings_layernorm.weight", 0, {h}});
-    e.push_back({"word_embeddings_layernorm.bias", 0, {h}});
-  }
-  static const char* tn[T_NLAYER] = {
-      "input_layernorm.weight", "input_layernorm.bias", "self_attention.query_key_value.weight",
-      "self_attention.query_key_value.bias", "self_attention.dense.weight", "self_attention.dense.bias",
-      "post_attention_layernorm.weight", "post_attention_layernorm.bias", "mlp.dense_h_to_4h.weight",
-      "mlp.dense_h_to_4h.bias", "mlp.dense_4h_to_h.weight", "mlp.dense_4h_to_h.bias"};
-  const std::vector<int64_t> ts[T_NLAYER] = {{h}, {h}, {3 * h, h}, {3 * h}, {h, h}, {h}, {h}, {h}, {4 * h, h}, {4 * h},
-                                             {h, 4 * h}, {h}};
-  for (int l = d->layer_begin; l < d->layer_end; l++)
-    for (int t = 0; t < T_NLAYER; t++) e.push_back({"h." + std::to_string(l) + "." + tn[t], 0, ts[t]});
-  if (d->is_last) { e.push_back({"ln_f.weight", 0, {h}}); e.push_back({"ln_f.bias", 0, {h}}); }
-  if (cls) e.push_back({"score.weight", 0, {(int64_t)d->n_labels, h}});  // BloomForSequenceClassification.score
-  const bool slice = d->head_vocab_end > d->head_vocab_begin;
-  if (slice && !d->is_first && !d->is_last) e.push_back({"word_embeddings.weight", (uint64_t)d->head_vocab_begin * h, {V, h}});
-  if (slice && !d->is_last) { e.push_back({"ln_f.weight", 0, {h}}); e.push_back({"ln_f.bias", 0, {h}}); }
-  return e;
-}
-static const st::Tensor* find_entry(const st::Checkpoint& ck, const FileEntry& fe, std::string* why) {
+// The checkpoint tensor of a weight-table entry, present, shaped right and of a loadable type (else null and why).
+static const st::Tensor* find_entry(const st::Checkpoint& ck, const WeightEntry& fe, std::string* why) {
   const st::Tensor* t = ck.find(fe.name);
   if (!t && fe.name == "word_embeddings.weight") t = ck.find("lm_head.weight");  // tied head saved alone
   if (!t) { *why = "checkpoint has no tensor '" + fe.name + "'"; return nullptr; }
@@ -442,7 +424,7 @@ extern "C" int bs_init_stage_file(const bs_stage_desc* desc, const char* path, b
   st::Checkpoint ck;
   std::string err;
   if (!ck.open(path, &err)) return fail(BS_ERR_INVALID, err);
-  for (const auto& fe : file_entries(desc))  // every tensor present and shaped right before any allocation
+  for (const WeightEntry& fe : weight_table(desc))  // every tensor present and shaped right before any allocation
     if (!find_entry(ck, fe, &err)) return fail(BS_ERR_INVALID, err);
   return init_stage(desc, out, &ck);
 }
@@ -498,130 +480,87 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   const size_t h = desc->hidden, V = desc->vocab, T = s->d.max_tokens;
 
   auto cleanup = [&](int code) { free_stage(s); return code; };
+#define INIT_TRY(expr)  /* HIP_TRY that frees the half-built stage */                                        \
+  do {                                                                                                       \
+    hipError_t e_ = (expr);                                                                                  \
+    if (e_ != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_))); \
+  } while (0)
   if (hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking) != hipSuccess)
     return cleanup(fail(BS_ERR_DEVICE, "hipStreamCreate failed"));
 
-  // ---- weight arena: every tensor 256-B aligned
-  std::vector<std::pair<void**, size_t>> plan;  // (slot, elements)
-  size_t off = 0;
-  std::vector<size_t> offs;
-  auto add = [&](size_t n) { offs.push_back(off); off = align_up(off + n * s->esz, 256); };
-  auto addb = [&](size_t bytes) { offs.push_back(off); off = align_up(off + bytes, 256); };
-  const bool own_emb = desc->is_first || (desc->is_last && !s->n_labels);
-  if (own_emb) add(V * h);
-  if (desc->is_first) { add(h); add(h); }
-  size_t lsz[T_NLAYER];
-  layer_sizes(h, lsz);
-  for (int l = 0; l < s->L; l++)
-    for (int t = 0; t < T_NLAYER; t++) {
-      if (s->q8 && is_matrix(t)) {
-        addb(lsz[t]);                                               // int8 [N][K]
-        addb((t == T_FC1_W ? 4 * h : (t == T_QKV_W ? 3 * h : h)) * 4);  // fp32 scale [N]
-      } else if (s->mx4 && is_matrix(t)) {
-        addb(lsz[t] / 2);                                           // E2M1 codes, 16-B block records
-        addb(lsz[t] / 32);                                          // E8M0 scale [N][K / 32]
-      } else {
-        add(lsz[t]);
-      }
+  // ---- weight arena: every tensor 256-B aligned, in table order; a quantised matrix is its codes, then its scales
+  s->weights = weight_table(desc);
+  Carver wa;
+  for (WeightEntry& w : s->weights) {
+    if (w.N && s->q8) {
+      wa.piece(&w.data, w.count);               // int8 [N][K]
+      wa.piece(&w.row_scale, (size_t)w.N * 4);  // fp32 scale [N]
+    } else if (w.N && s->mx4) {
+      wa.piece(&w.data, w.count / 2);           // E2M1 codes, 16-B block records
+      wa.piece(&w.blk_scale, w.count / 32);     // E8M0 scale [N][K / 32]
+    } else {
+      wa.piece(&w.data, w.count * s->esz);
     }
-  if (desc->is_last) { add(h); add(h); }
-  if (s->n_labels) add((size_t)s->n_labels * h);
-  const bool slice = desc->head_vocab_end > desc->head_vocab_begin;
+  }
+  s->wbytes = wa.total;
+  if (wa.alloc() != Carver::OK)
+    return cleanup(fail(BS_ERR_OOM, "weight allocation failed (" + std::to_string(s->wbytes) + " B)"));
+  s->owned.push_back({wa.base, 0});
+  s->layers.assign(s->L, Layer{});
+  void** const model_slot[] = {&s->wemb, &s->emb_g, &s->emb_b, &s->lnf_g, &s->lnf_b, &s->score, &s->hw};  // by M_*
+  for (const WeightEntry& w : s->weights) {
+    if (w.layer < 0) {
+      *model_slot[w.tid] = w.data;
+    } else {
+      Layer& ly = s->layers[w.layer];
+      ly.t[w.tid] = w.data; ly.sc[w.tid] = w.row_scale; ly.mxs[w.tid] = w.blk_scale;
+    }
+  }
   s->hv0 = desc->head_vocab_begin;
   s->hv1 = desc->head_vocab_end;
-  const size_t hrows = (size_t)(s->hv1 - s->hv0);
-  if (slice && !desc->is_first && !desc->is_last) add(hrows * h);
-  if (slice && !desc->is_last) { add(h); add(h); }
-  s->wbytes = off;
-  if (hipMalloc(&s->wbase, s->wbytes ? s->wbytes : 256) != hipSuccess)
-    return cleanup(fail(BS_ERR_OOM, "weight allocation failed (" + std::to_string(s->wbytes) + " B)"));
-  size_t oi = 0;
-  if (own_emb) s->wemb = s->wbase + offs[oi++];
-  if (desc->is_first) { s->emb_g = s->wbase + offs[oi++]; s->emb_b = s->wbase + offs[oi++]; }
-  s->layers.resize(s->L);
-  for (int l = 0; l < s->L; l++)
-    for (int t = 0; t < T_NLAYER; t++) {
-      s->layers[l].t[t] = s->wbase + offs[oi++];
-      s->layers[l].sc[t] = (s->q8 && is_matrix(t)) ? (float*)(s->wbase + offs[oi++]) : nullptr;
-      s->layers[l].mxs[t] = (s->mx4 && is_matrix(t)) ? (uint8_t*)(s->wbase + offs[oi++]) : nullptr;
-    }
-  if (desc->is_last) { s->lnf_g = s->wbase + offs[oi++]; s->lnf_b = s->wbase + offs[oi++]; }
-  if (s->n_labels) s->score = s->wbase + offs[oi++];
-  if (slice) {
-    if (s->wemb) s->hw = (char*)s->wemb + (size_t)s->hv0 * h * s->esz;
-    else s->hw = s->wbase + offs[oi++];
-    if (!desc->is_last) { s->lnf_g = s->wbase + offs[oi++]; s->lnf_b = s->wbase + offs[oi++]; }
+  if (has_head_slice(desc)) {
+    if (s->wemb) s->hw = (char*)s->wemb + (size_t)s->hv0 * h * s->esz;  // else its own tensor (M_HEAD)
   } else if (desc->is_last && !s->n_labels) {
     s->hw = s->wemb; s->hv0 = 0; s->hv1 = desc->vocab;  // the last stage's full head
   }
-  if (s->wemb) s->order.push_back({s->wemb, V * h});
-  if (s->emb_g) { s->order.push_back({s->emb_g, h}); s->order.push_back({s->emb_b, h}); }
-  for (int l = 0; l < s->L; l++)
-    for (int t = 0; t < T_NLAYER; t++) s->order.push_back({s->layers[l].t[t], lsz[t]});
-  if (desc->is_last) { s->order.push_back({s->lnf_g, h}); s->order.push_back({s->lnf_b, h}); }
-  if (s->score) s->order.push_back({s->score, (size_t)s->n_labels * h});
-  if (slice && !desc->is_first && !desc->is_last) s->order.push_back({s->hw, hrows * h});
-  if (slice && !desc->is_last) { s->order.push_back({s->lnf_g, h}); s->order.push_back({s->lnf_b, h}); }
-  s->order_q8.assign(s->order.size(), {nullptr, 0});
-  if (s->q8) {
-    for (size_t i = 0; i < s->order.size(); i++)
-      for (int l = 0; l < s->L; l++)
-        for (int t = 0; t < T_NLAYER; t++)
-          if (s->layers[l].sc[t] && s->order[i].first == s->layers[l].t[t])
-            s->order_q8[i] = {s->layers[l].sc[t], (int)(t == T_FC2_W ? 4 * h : h)};
-    if (hipMalloc(&s->wtmp, 4 * h * h * 2) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "int8 staging allocation failed"));
-  }
-  s->order_mx.assign(s->order.size(), {nullptr, 0});
-  if (s->mx4) {
-    for (size_t i = 0; i < s->order.size(); i++)
-      for (int l = 0; l < s->L; l++)
-        for (int t = 0; t < T_NLAYER; t++)
-          if (s->layers[l].mxs[t] && s->order[i].first == s->layers[l].t[t])
-            s->order_mx[i] = {s->layers[l].mxs[t], (int)(t == T_FC2_W ? 4 * h : h)};
-    if (hipMalloc(&s->wtmp, 4 * h * h * 2) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "MXFP4 staging allocation failed"));
-  }
+  if ((s->q8 || s->mx4) && !owned_alloc(s, 4 * h * h * 2, false, &s->wtmp))
+    return cleanup(fail(BS_ERR_OOM, std::string(s->q8 ? "int8" : "MXFP4") + " staging allocation failed"));
   // int8 / MXFP4 matrices are produced in bf16 in the staging buffer, then quantized into the arena
-  auto staged = [&](size_t i) { return s->order_q8[i].first != nullptr || s->order_mx[i].first != nullptr; };
-  auto quantize = [&](size_t i) {
-    if (s->order_mx[i].first) {
-      const int K = s->order_mx[i].second, N = (int)(s->order[i].second / K);
-      launch_quantize_mx4(s->wtmp, (uint8_t*)s->order[i].first, (uint8_t*)s->order_mx[i].first, N, K, s->own);
-      return;
-    }
-    const int K = s->order_q8[i].second, N = (int)(s->order[i].second / K);
-    launch_quantize_rows(s->wtmp, (int8_t*)s->order[i].first, (float*)s->order_q8[i].first, N, K, s->own);
+  auto target = [&](const WeightEntry& w) { return (char*)(w.quantised() ? s->wtmp : w.data); };
+  auto quantize = [&](const WeightEntry& w) {
+    if (w.blk_scale) launch_quantize_mx4(s->wtmp, (uint8_t*)w.data, w.blk_scale, w.N, w.K, s->own);
+    else if (w.row_scale) launch_quantize_rows(s->wtmp, (int8_t*)w.data, w.row_scale, w.N, w.K, s->own);
   };
 
-  // ---- weights
+  // ---- weights: the three sources walk the table
+  const size_t chunk = 16u << 20;
+  // fp32 chunks on their way to the stage's type (file and host sources), freed on every path
+  struct Bounce { float* p = nullptr; ~Bounce() { hipFree(p); } } bounce;
+  auto upload_f32 = [&](char* dst, const float* src, size_t n) {
+    if (hipMemcpyAsync(bounce.p, src, n * sizeof(float), hipMemcpyHostToDevice, s->own) != hipSuccess) return false;
+    launch_convert_f32(dst, s->bf16, bounce.p, n, s->own);
+    return true;
+  };
   if (ck) {
     // Straight from the file mapping: matching dtypes are copied as they are, others widen to fp32 on
     // the host (exact) and take the BS_WEIGHTS_HOST conversion, so a file of fp32 weights loads
     // bit-identical to the same weights passed as a host buffer.
-    const std::vector<FileEntry> fes = file_entries(desc);
-    if (fes.size() != s->order.size()) return cleanup(fail(BS_ERR_STATE, "checkpoint entry list out of step"));
-    const size_t chunk = 16u << 20;
     std::vector<float> wide(chunk);
-    float* bounce = nullptr;
-    if (hipMalloc(&bounce, chunk * sizeof(float)) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "bounce alloc"));
+    if (hipMalloc(&bounce.p, chunk * sizeof(float)) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "bounce alloc"));
     std::string why;
-    for (size_t oi2 = 0; oi2 < s->order.size(); oi2++) {
-      const auto& o = s->order[oi2];
-      const bool q = staged(oi2);
-      char* dst = (char*)(q ? s->wtmp : o.first);
-      const st::Tensor* t = find_entry(*ck, fes[oi2], &why);
-      if (!t || fes[oi2].first + o.second > t->numel()) {
-        hipFree(bounce);
+    for (const WeightEntry& w : s->weights) {
+      const st::Tensor* t = find_entry(*ck, w, &why);
+      if (!t || w.first + w.count > t->numel())
         return cleanup(fail(BS_ERR_INVALID, t ? "head slice outside the checkpoint's embedding" : why));
-      }
       const bool same = (s->bf16 && t->dtype == st::BF16) || (!s->bf16 && t->dtype == st::F32);
       const size_t tes = t->dtype == st::F32 ? 4 : 2;
-      const uint8_t* src = t->data + fes[oi2].first * tes;
+      const uint8_t* src = t->data + w.first * tes;
       bool ok = true;
       if (same) {
-        ok = hipMemcpyAsync(dst, src, o.second * s->esz, hipMemcpyHostToDevice, s->own) == hipSuccess;
+        ok = hipMemcpyAsync(target(w), src, w.count * s->esz, hipMemcpyHostToDevice, s->own) == hipSuccess;
       } else {
-        for (size_t i = 0; ok && i < o.second; i += chunk) {
-          const size_t n = std::min(chunk, o.second - i);
+        for (size_t i = 0; ok && i < w.count; i += chunk) {
+          const size_t n = std::min<size_t>(chunk, w.count - i);
           const uint8_t* p = src + i * tes;
           if (t->dtype == st::F32) {
             std::memcpy(wide.data(), p, n * 4);
@@ -637,65 +576,35 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
               }
             }
           }
-          ok = hipMemcpyAsync(bounce, wide.data(), n * sizeof(float), hipMemcpyHostToDevice, s->own) == hipSuccess;
-          if (ok) launch_convert_f32(dst + i * s->esz, s->bf16, bounce, n, s->own);
-          ok = ok && hipStreamSynchronize(s->own) == hipSuccess;  // `wide` is refilled next round
+          ok = upload_f32(target(w) + i * s->esz, wide.data(), n) &&
+               hipStreamSynchronize(s->own) == hipSuccess;  // `wide` is refilled next round
         }
       }
-      if (ok && q) quantize(oi2);
-      if (!ok) {
-        hipFree(bounce);
-        return cleanup(fail(BS_ERR_DEVICE, "weight upload failed"));
-      }
+      if (!ok) return cleanup(fail(BS_ERR_DEVICE, "weight upload failed"));
+      quantize(w);
     }
-    const bool synced = hipStreamSynchronize(s->own) == hipSuccess;  // the mapping goes away after init
-    hipFree(bounce);
-    if (!synced) return cleanup(fail(BS_ERR_DEVICE, "weight upload failed"));
+    if (hipStreamSynchronize(s->own) != hipSuccess)  // the mapping goes away after init
+      return cleanup(fail(BS_ERR_DEVICE, "weight upload failed"));
   } else if (desc->weight_source == BS_WEIGHTS_SYNTHETIC) {
-    const uint64_t seed = desc->seed;
-    if (s->wemb) launch_gen_fill(s->wemb, s->bf16, V * h, tensor_key(seed, -1, M_WEMB), 0, s->own);
-    if (s->emb_g) launch_gen_fill(s->emb_g, s->bf16, h, tensor_key(seed, -1, M_EMB_G), 2, s->own);
-    if (s->emb_b) launch_gen_fill(s->emb_b, s->bf16, h, tensor_key(seed, -1, M_EMB_B), 3, s->own);
-    for (int l = 0; l < s->L; l++)
-      for (int t = 0; t < T_NLAYER; t++) {
-        const bool q = s->layers[l].sc[t] != nullptr || s->layers[l].mxs[t] != nullptr;
-        launch_gen_fill(q ? s->wtmp : s->layers[l].t[t], s->bf16, lsz[t], tensor_key(seed, desc->layer_begin + l, t),
-                        layer_kind(t), s->own);
-        if (q) {
-          for (size_t i = 0; i < s->order.size(); i++)
-            if (s->order[i].first == s->layers[l].t[t]) quantize(i);
-        }
-      }
-    if (slice && !s->wemb)
-      launch_gen_fill(s->hw, s->bf16, hrows * h, tensor_key(seed, -1, M_WEMB), 0, s->own, (uint64_t)s->hv0 * h);
-    if (s->lnf_g) launch_gen_fill(s->lnf_g, s->bf16, h, tensor_key(seed, -1, M_LNF_G), 2, s->own);
-    if (s->lnf_b) launch_gen_fill(s->lnf_b, s->bf16, h, tensor_key(seed, -1, M_LNF_B), 3, s->own);
-    if (s->score) launch_gen_fill(s->score, s->bf16, (size_t)s->n_labels * h, tensor_key(seed, -1, M_SCORE), 0, s->own);
+    for (const WeightEntry& w : s->weights) {
+      launch_gen_fill(target(w), s->bf16, w.count, w.key, w.kind, s->own, w.first);
+      quantize(w);
+    }
   } else {
     const uint64_t need = bs_stage_weight_count(desc);
     if (!desc->host_weights || desc->host_weight_count != need)
       return cleanup(fail(BS_ERR_INVALID, "host_weights count mismatch: need " + std::to_string(need)));
     // canonical order == arena order; upload through an fp32 bounce buffer
-    const size_t chunk = 16u << 20;
-    float* bounce = nullptr;
-    if (hipMalloc(&bounce, chunk * sizeof(float)) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "bounce alloc"));
+    if (hipMalloc(&bounce.p, chunk * sizeof(float)) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "bounce alloc"));
     const float* src = desc->host_weights;
-    for (size_t oi2 = 0; oi2 < s->order.size(); oi2++) {
-      const auto& o = s->order[oi2];
-      const bool q = staged(oi2);
-      for (size_t i = 0; i < o.second; i += chunk) {
-        const size_t n = std::min(chunk, o.second - i);
-        if (hipMemcpyAsync(bounce, src + i, n * sizeof(float), hipMemcpyHostToDevice, s->own) != hipSuccess) {
-          hipFree(bounce);
+    for (const WeightEntry& w : s->weights) {
+      for (size_t i = 0; i < w.count; i += chunk)
+        if (!upload_f32(target(w) + i * s->esz, src + i, std::min<size_t>(chunk, w.count - i)))
           return cleanup(fail(BS_ERR_DEVICE, "weight upload failed"));
-        }
-        launch_convert_f32((char*)(q ? s->wtmp : o.first) + i * s->esz, s->bf16, bounce, n, s->own);
-      }
-      if (q) quantize(oi2);
-      src += o.second;
+      quantize(w);
+      src += w.count;
     }
     hipStreamSynchronize(s->own);
-    hipFree(bounce);
   }
 
   // ---- greedy lm_head screening: int8 shadow copy of the resident bf16 embedding (the BS_FLAG_INT8_WEIGHTS rule),
@@ -703,24 +612,27 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   if (s->bf16 && desc->is_last && !s->n_labels && s->wemb && head_screen_supported(1, (int)h) &&
       hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, desc->device) == hipSuccess && s->cus > 0) {
     const size_t nt = V / 16, mb = std::min<size_t>(desc->max_batch, 2);
-    const size_t sizes[8] = {V * h, V * 4, V * 4, mb * nt * 8, mb * 4, mb * 4, mb * nt * 4, mb * 4};
-    size_t ho[8], hoff = 0;
-    for (int i = 0; i < 8; i++) { ho[i] = hoff; hoff = align_up(hoff + sizes[i], 256); }
-    if (hipMalloc(&s->hs_base, hoff) == hipSuccess) {
-      s->hs_bytes = hoff;
-      int8_t* Qh = (int8_t*)(s->hs_base + ho[0]);
-      float* sch = (float*)(s->hs_base + ho[1]);
-      float* cbh = (float*)(s->hs_base + ho[2]);
-      s->hs = HeadScreen{Qh, sch, cbh, (float*)(s->hs_base + ho[3]), (float*)(s->hs_base + ho[4]),
-                         (float*)(s->hs_base + ho[5]), (int*)(s->hs_base + ho[6]), (int*)(s->hs_base + ho[7])};
-      if (hipMemsetAsync(s->hs_base + ho[3], 0, hoff - ho[3], s->own) != hipSuccess)
+    int8_t* Qh = nullptr;
+    float *sch = nullptr, *cbh = nullptr;
+    Carver c;
+    c.piece(&Qh, V * h);
+    c.piece(&sch, V * 4);
+    c.piece(&cbh, V * 4);
+    c.piece(&s->hs.hilo, mb * nt * 8);
+    c.piece(&s->hs.rnorm, mb * 4);
+    c.piece(&s->hs.lstar, mb * 4);
+    c.piece(&s->hs.list, mb * nt * 4);
+    c.piece(&s->hs.count, mb * 4);
+    if (c.alloc() == Carver::OK) {
+      s->owned.push_back({c.base, c.total});
+      s->hs.Q = Qh; s->hs.scale = sch; s->hs.cb = cbh;
+      if (hipMemsetAsync(s->hs.hilo, 0, c.base + c.total - (char*)s->hs.hilo, s->own) != hipSuccess)  // the per-step buffers
         return cleanup(fail(BS_ERR_DEVICE, "head screen memset"));
       launch_quantize_rows(s->wemb, Qh, sch, (int)V, (int)h, s->own);
       launch_head_bound(s->wemb, Qh, sch, cbh, (int)V, (int)h, s->own);
       s->hs_on = head_screen_default();
     } else {
       (void)hipGetLastError();  // not an init failure
-      s->hs_base = nullptr;
     }
   }
 
@@ -733,7 +645,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
     s->kvbytes += 2 * s->kv_sc_half * 4 * (s->L > 0 ? s->L : 0);
   }
   if (s->kvbytes) {
-    if (hipMalloc(&s->kv, s->kvbytes) != hipSuccess)
+    if (!owned_alloc(s, s->kvbytes, false, (void**)&s->kv))
       return cleanup(fail(BS_ERR_OOM, "KV cache allocation failed (" + std::to_string(s->kvbytes) + " B)"));
     if (hipMemsetAsync(s->kv, 0, s->kvbytes, s->own) != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, "kv memset"));
     if (s->kv8) s->kv_scales = (float*)(s->kv + s->kv_layer_stride * s->L);
@@ -741,7 +653,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   if (s->kv8 && s->L > 0) {  // bf16 staging of a call's new K / V rows (and, for S > 1, the dequantised past)
     s->kv_stage_cap = std::max<size_t>(T, desc->max_ctx);
     const size_t sb = 2 * s->kv_stage_cap * h * 2;
-    if (hipMalloc(&s->kv_stage, sb) != hipSuccess)
+    if (!owned_alloc(s, sb, true, (void**)&s->kv_stage))
       return cleanup(fail(BS_ERR_OOM, "KV staging allocation failed (" + std::to_string(sb) + " B)"));
     if (hipMemsetAsync(s->kv_stage, 0, sb, s->own) != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, "kv staging memset"));
   }
@@ -749,55 +661,39 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   // ---- workspace
   const size_t attn_f = attention_workspace_floats(desc->max_batch, desc->n_head, s->hd, desc->max_ctx, &s->max_chunks,
                                                    &s->chunk);
-  std::vector<size_t> wo;
-  size_t woff = 0;
-  auto wadd = [&](size_t bytes) { wo.push_back(woff); woff = align_up(woff + bytes, 256); };
-  wadd(T * h * 4);       // xa
-  wadd(T * h * 4);       // xb
-  wadd(T * h * 4);       // attn
-  wadd(T * h * 4);       // q
-  wadd(T * h * s->esz);  // xn
-  wadd(T * h * s->esz);  // ctx
-  wadd(T * 4 * h * s->esz);  // g
-  wadd(attn_f * 4);      // partials
-  wadd(desc->n_head * 4);
-  wadd((size_t)desc->max_batch * (V / 16) * 8);
-  wadd((size_t)desc->max_batch * 4);
-  wadd(T * 4);
-  wadd((size_t)desc->max_batch * 4);                 // per-row past_len (device copy)
-  wadd((size_t)desc->max_batch * desc->n_head * 4);  // attention split-merge tickets
-  wadd(kSkCap * 4);                                  // batched-GEMV split-K partials
-  wadd(kSkTickets * 4);                              // and their tickets
-  s->wsbytes = woff;
-  if (hipMalloc(&s->ws, s->wsbytes) != hipSuccess) return cleanup(fail(BS_ERR_OOM, "workspace allocation failed"));
-  int wi = 0;
-  s->xa = (float*)(s->ws + wo[wi++]);
-  s->xb = (float*)(s->ws + wo[wi++]);
-  s->attn = (float*)(s->ws + wo[wi++]);
-  s->q = s->ws + wo[wi++];
-  s->xn = s->ws + wo[wi++];
-  s->ctx = s->ws + wo[wi++];
-  s->g = s->ws + wo[wi++];
-  s->part_acc = (float*)(s->ws + wo[wi++]);
+  Carver wc;
+  wc.piece(&s->xa, T * h * 4);
+  wc.piece(&s->xb, T * h * 4);
+  wc.piece(&s->attn, T * h * 4);
+  wc.piece(&s->q, T * h * 4);
+  wc.piece(&s->xn, T * h * s->esz);
+  wc.piece(&s->ctx, T * h * s->esz);
+  wc.piece(&s->g, T * 4 * h * s->esz);
+  wc.piece(&s->part_acc, attn_f * 4);  // part_ml follows
+  wc.piece(&s->slopes, desc->n_head * 4);
+  wc.piece(&s->keys, (size_t)desc->max_batch * (V / 16) * 8);
+  wc.piece(&s->tok, (size_t)desc->max_batch * 4);
+  wc.piece(&s->ids, T * 4);
+  wc.piece(&s->past_dev, (size_t)desc->max_batch * 4);                     // per-row past_len (device copy)
+  wc.piece(&s->att_tickets, (size_t)desc->max_batch * desc->n_head * 4);   // attention split-merge tickets
+  wc.piece(&s->sk_ws, kSkCap * 4);                                         // batched-GEMV split-K partials
+  wc.piece(&s->sk_tickets, kSkTickets * 4);                                // and their tickets
+  s->wsbytes = wc.total;
+  if (wc.alloc() != Carver::OK) return cleanup(fail(BS_ERR_OOM, "workspace allocation failed"));
+  s->owned.push_back({wc.base, 0});
+  s->ws = wc.base;
   s->part_ml = s->part_acc + (size_t)desc->max_batch * desc->n_head * s->max_chunks * s->hd;
-  s->slopes = (float*)(s->ws + wo[wi++]);
-  s->keys = (unsigned long long*)(s->ws + wo[wi++]);
-  s->tok = (int*)(s->ws + wo[wi++]);
-  s->ids = (int*)(s->ws + wo[wi++]);
-  s->past_dev = (int*)(s->ws + wo[wi++]);
-  s->att_tickets = (unsigned*)(s->ws + wo[wi++]);
-  s->sk_ws = (float*)(s->ws + wo[wi++]);
-  s->sk_tickets = (unsigned*)(s->ws + wo[wi++]);
-  HIP_TRY(hipMemsetAsync(s->ws, 0, s->wsbytes, s->own));
   std::vector<float> sl(desc->n_head);
   alibi_slopes(desc->n_head, sl.data());
-  HIP_TRY(hipMemcpyAsync(s->slopes, sl.data(), sl.size() * 4, hipMemcpyHostToDevice, s->own));
+  INIT_TRY(hipMemsetAsync(s->ws, 0, s->wsbytes, s->own));
+  INIT_TRY(hipMemcpyAsync(s->slopes, sl.data(), sl.size() * 4, hipMemcpyHostToDevice, s->own));
   hipError_t e = hipStreamSynchronize(s->own);
   if (e != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, std::string("init sync: ") + hipGetErrorString(e)));
   e = hipGetLastError();
   if (e != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, std::string("init kernels: ") + hipGetErrorString(e)));
   *out = s;
   return BS_OK;
+#undef INIT_TRY
 }
 
 extern "C" void bs_release(bs_stage* s) { free_stage(s); }
@@ -807,8 +703,11 @@ extern "C" int bs_stage_info(const bs_stage* s, bs_stage_desc* d, uint64_t* wb, 
   if (d) *d = s->d;
   if (wb) *wb = s->wbytes;
   if (kvb) *kvb = s->kvbytes;
-  // the head-screening shadow copy, the int8 KV staging, the scoring and the verify buffers count as workspace
-  if (wsb) *wsb = s->wsbytes + s->hs_bytes + s->sc_bytes + s->vf_bytes + s->rs_bytes + s->vd_bytes + (s->kv_stage ? 2 * s->kv_stage_cap * s->d.hidden * 2 : 0);
+  // the head-screening shadow copy, the int8 KV staging, the scoring, verify and sampler buffers count as workspace
+  if (wsb) {
+    *wsb = s->wsbytes;
+    for (const OwnedAlloc& a : s->owned) *wsb += a.counted;
+  }
   return BS_OK;
 }
 
@@ -821,22 +720,22 @@ extern "C" int bs_read_weights(const bs_stage* s, uint64_t offset, uint64_t coun
   std::vector<int8_t> qtmp;
   std::vector<float> stmp;
   std::vector<uint8_t> ctmp, etmp;
-  for (size_t oi = 0; oi < s->order.size(); oi++) {
-    const auto& o = s->order[oi];
-    const uint64_t b = base, e = base + o.second;
+  for (const WeightEntry& w : s->weights) {
+    const uint64_t b = base, e = base + w.count;
     base = e;
     if (e <= offset || b >= offset + count) continue;
     const uint64_t lo = std::max<uint64_t>(b, offset), hi = std::min<uint64_t>(e, offset + count);
     const uint64_t n = hi - lo;
-    const char* src = (const char*)o.first + (lo - b) * s->esz;
+    const char* src = (const char*)w.data + (lo - b) * s->esz;
     float* dst = out + (lo - offset);
-    if (s->order_mx[oi].first) {  // MXFP4 matrix: +-grid[code] * 2^(E - 127), codes in rotated block records
-      const int K = s->order_mx[oi].second, nb = K / 32;
+    const int K = w.K;
+    if (w.blk_scale) {  // MXFP4 matrix: +-grid[code] * 2^(E - 127), codes in rotated block records
+      const int nb = K / 32;
       const uint64_t b0 = (lo - b) / 32, b1 = (hi - b - 1) / 32;  // blocks of the matrix, row-major
       ctmp.resize((b1 - b0 + 1) * 16);
       etmp.resize(b1 - b0 + 1);
-      HIP_TRY(hipMemcpy(ctmp.data(), (const uint8_t*)o.first + b0 * 16, ctmp.size(), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(etmp.data(), s->order_mx[oi].first + b0, etmp.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(ctmp.data(), (const uint8_t*)w.data + b0 * 16, ctmp.size(), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(etmp.data(), w.blk_scale + b0, etmp.size(), hipMemcpyDeviceToHost));
       static const float grid[16] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f, -0.f, -0.5f, -1.f, -1.5f, -2.f, -3.f, -4.f, -6.f};
       for (uint64_t blk = b0; blk <= b1; blk++) {
         const float X = std::ldexp(1.0f, (int)etmp[blk - b0] - 127);
@@ -853,13 +752,12 @@ extern "C" int bs_read_weights(const bs_stage* s, uint64_t offset, uint64_t coun
         const uint64_t k0 = std::max<uint64_t>(blk * 32, lo - b), k1 = std::min<uint64_t>(blk * 32 + 32, hi - b);
         for (uint64_t k = k0; k < k1; k++) dst[k - (lo - b)] = v[k - blk * 32];
       }
-    } else if (s->order_q8[oi].first) {  // int8 matrix: dequantized values Q * scale
-      const int K = s->order_q8[oi].second;
+    } else if (w.row_scale) {  // int8 matrix: dequantized values Q * scale
       const uint64_t r0 = (lo - b) / K, r1 = (hi - b - 1) / K;
       qtmp.resize(n);
       stmp.resize(r1 - r0 + 1);
-      HIP_TRY(hipMemcpy(qtmp.data(), (const int8_t*)o.first + (lo - b), n, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(stmp.data(), s->order_q8[oi].first + r0, stmp.size() * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(qtmp.data(), (const int8_t*)w.data + (lo - b), n, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(stmp.data(), w.row_scale + r0, stmp.size() * 4, hipMemcpyDeviceToHost));
       for (uint64_t i = 0; i < n; i++) dst[i] = (float)qtmp[i] * stmp[(lo - b + i) / K - r0];
     } else if (s->bf16) {
       tmp.resize(n);
@@ -1233,15 +1131,20 @@ static bool rows_sampled(const bs_stage* s, int slot, int B) {
   return false;
 }
 
-// Does a verify pass with these flags end in the row sampler at every position (else the argmax tail)?
-static bool verify_draws(const bs_stage* s, int flags, int slot, int B) {
-  return (flags & BS_STEP_VERIFY) && (flags & BS_STEP_VERIFY_DRAW) && s->d.is_last && rows_sampled(s, slot, B);
-}
-
-// Does a forward of B rows at `slot` take the screened greedy tail (else the full head)?
-static bool head_screened(const bs_stage* s, int slot, int B, bool want_logits) {
-  return s->hs_on && s->hs_base && s->d.is_last && !s->n_labels && s->top_k <= 1 && !want_logits &&
-         head_screen_supported(B, s->d.hidden) && !rows_sampled(s, slot, B);
+// Which tail this pass ends in (scoring: a bs_forward_score pass).  forward_impl has checked the step against the stage.
+static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring) {
+  const int B = step->batch, M = B * step->seq, V = s->d.vocab;
+  if (!s->d.is_last) return Tail{};
+  if (s->n_labels) return Tail{TAIL_CLASSIFY, B, s->n_labels};
+  if (scoring) return Tail{TAIL_SCORE, M, V};
+  const bool rows = rows_sampled(s, step->slot, B);  // excludes top_k > 1 (bs_set_row_sampler / bs_set_sampling)
+  if (step->flags & BS_STEP_VERIFY)
+    return Tail{rows && (step->flags & BS_STEP_VERIFY_DRAW) ? TAIL_VERIFY_DRAW : TAIL_VERIFY_ARGMAX, M, V};
+  if (rows) return Tail{TAIL_ROWS, B, V};
+  if (s->top_k > 1) return Tail{TAIL_TOPK, B, V};
+  if (s->hs_on && s->hs.Q && !(step->flags & BS_STEP_LOGITS) && head_screen_supported(B, s->d.hidden))
+    return Tail{TAIL_SCREENED, B, V};
+  return Tail{TAIL_GREEDY, B, V};
 }
 
 // Device staging for logits requested with host I/O: one buffer per stage, grown on demand (a
@@ -1250,27 +1153,55 @@ static bool head_screened(const bs_stage* s, int slot, int B, bool want_logits) 
 static int logits_staging(bs_stage* s, size_t bytes, hipStream_t st, float** out) {
   if (bytes > s->logit_cap) {
     HIP_TRY(hipStreamSynchronize(st));
-    if (s->logit_buf) HIP_TRY(hipFree(s->logit_buf));
+    if (s->logit_buf) {
+      s->owned.erase(std::find_if(s->owned.begin(), s->owned.end(), [&](const OwnedAlloc& a) { return a.p == s->logit_buf; }));
+      HIP_TRY(hipFree(s->logit_buf));
+    }
     s->logit_buf = nullptr;
     s->logit_cap = 0;
-    if (hipMalloc((void**)&s->logit_buf, bytes) != hipSuccess) return fail(BS_ERR_OOM, "logits staging allocation failed");
+    if (!owned_alloc(s, bytes, false, (void**)&s->logit_buf)) return fail(BS_ERR_OOM, "logits staging allocation failed");
     s->logit_cap = bytes;
   }
   *out = s->logit_buf;
   return BS_OK;
 }
 
+// Where a tail's head writes its logits: the caller's device buffer, with host I/O the staging (*staged, which
+// tail_copy_out copies to the caller), else `priv`, the buffer the kind's own pick reads (null: none are written).
+static int tail_logits(bs_stage* s, const Tail& t, const bs_step* step, float* caller, float* priv, hipStream_t st,
+                       float** dev, float** staged) {
+  *staged = nullptr;
+  *dev = priv;
+  if (!(step->flags & BS_STEP_LOGITS)) return BS_OK;
+  if (!(step->flags & BS_STEP_HOST_IO)) {
+    *dev = caller;
+    return BS_OK;
+  }
+  int rc = logits_staging(s, (size_t)t.rows * t.width * 4, st, staged);
+  if (rc == BS_OK) *dev = *staged;
+  return rc;
+}
+
+// Host I/O: the tail's ids from their device staging `tok` to `out`, the staged logits to the caller's buffer.
+static int tail_copy_out(const Tail& t, const bs_step* step, const int* tok, void* out, const float* staged,
+                         float* logits, hipStream_t st) {
+  if (!(step->flags & BS_STEP_HOST_IO)) return BS_OK;
+  HIP_TRY(hipMemcpyAsync(out, tok, (size_t)t.rows * 4, hipMemcpyDeviceToHost, st));
+  if (staged) HIP_TRY(hipMemcpyAsync(logits, staged, (size_t)t.rows * t.width * 4, hipMemcpyDeviceToHost, st));
+  return BS_OK;
+}
+
 // Enqueue one forward on `st`.  The kernels read each row's past_len from past_dev (device [B],
 // written ahead of the forward or of the graph replay); `pasts` is the host copy (profiling bytes).
-// sc (bs_forward_score): the tail scores every position instead of picking each row's next token.
-static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, hipStream_t st,
-                           const int* past_dev, const std::vector<int>& pasts, const ScoreIO* sc = nullptr) {
+// tail: what forward_impl planned; sc: what a TAIL_SCORE reads and writes (bs_forward_score).
+static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, const void* in, void* out, float* logits,
+                           hipStream_t st, const int* past_dev, const std::vector<int>& pasts,
+                           const ScoreIO* sc = nullptr) {
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot, past = pasts[0];
   double ctx_sum = 0.0;
   for (int b = 0; b < B; b++) ctx_sum += (double)pasts[b] + S;
   const int M = B * S;
-  const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
   const bool verify = (step->flags & BS_STEP_VERIFY) != 0;  // forward_impl checked the shape and the stage
   const int h = d.hidden, V = d.vocab, hd = s->hd, nh = d.n_head;
@@ -1383,113 +1314,94 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const void* in, voi
     cur = nxt;
   }
 
-  // ---- output
-  if (d.is_last && s->n_labels) {
-    // sequence-classification tail (run_inference_with_binary_classification, inference.cpp:220-270): ln_f on each
-    // row's last position, score, first maximal class; the class kernel is the step's last (advances past_dev)
-    float* dev_logits = want_logits && !host_io ? logits : nullptr;
-    if (want_logits && host_io) {
-      int rc = logits_staging(s, (size_t)B * s->n_labels * 4, st, &dev_logits);
-      if (rc != BS_OK) return rc;
+  // ---- output: the tail forward_impl planned.  Each tail's last kernel advances past_dev by S for the B rows.
+  int rc = BS_OK;
+  float* staged = nullptr;  // host-I/O logits on their way to the caller
+  switch (tail.kind) {
+    case TAIL_NONE:
+      if (host_io) HIP_TRY(hipMemcpyAsync(out, cur, (size_t)M * h * 4, hipMemcpyDeviceToHost, st));
+      else if (s->L == 0) HIP_TRY(hipMemcpyAsync(out, cur, (size_t)M * h * 4, hipMemcpyDeviceToDevice, st));
+      break;
+    case TAIL_CLASSIFY: {
+      // sequence-classification tail (run_inference_with_binary_classification, inference.cpp:220-270): ln_f on each
+      // row's last position, score, first maximal class
+      float* dev_logits = nullptr;
+      if ((rc = tail_logits(s, tail, step, logits, nullptr, st, &dev_logits, &staged)) != BS_OK) return rc;
+      launch_layernorm(s->bf16, cur, nullptr, S, S - 1, s->lnf_g, s->lnf_b, s->xn, 0, B, h, d.ln_eps, st);
+      launch_classify(s->bf16, s->xn, s->score, B, s->n_labels, h, dev_logits, host_io ? s->tok : (int*)out, s->past_dev,
+                      S, st);
+      return tail_copy_out(tail, step, s->tok, out, staged, logits, st);
     }
-    launch_layernorm(s->bf16, cur, nullptr, S, S - 1, s->lnf_g, s->lnf_b, s->xn, 0, B, h, d.ln_eps, st);
-    int* cls_out = host_io ? s->tok : (int*)out;
-    launch_classify(s->bf16, s->xn, s->score, B, s->n_labels, h, dev_logits, cls_out, s->past_dev, S, st);
-    if (host_io) {
-      HIP_TRY(hipMemcpyAsync(out, s->tok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-      if (dev_logits)
-        HIP_TRY(hipMemcpyAsync(logits, dev_logits, (size_t)B * s->n_labels * 4, hipMemcpyDeviceToHost, st));
-    }
-  } else if (d.is_last && sc) {
-    // teacher-forced scoring: ln_f of all M positions -> xn, then the tied lm_head fused with a log-softmax
-    // (head_score.hip); its merge kernel is the pass's last and advances past_dev by S
-    const int* tg = sc->targets;
-    if (host_io && tg) {
-      HIP_TRY(hipMemcpyAsync(s->sc_targets, tg, (size_t)M * 4, hipMemcpyHostToDevice, st));
-      tg = s->sc_targets;
-    }
-    int* top = sc->top_ids ? (host_io ? s->sc_top : sc->top_ids) : nullptr;
-    float* scr = sc->scores ? (host_io ? s->sc_scores : sc->scores) : nullptr;
-    launch_layernorm(s->bf16, cur, nullptr, 1, 0, s->lnf_g, s->lnf_b, s->xn, 0, M, h, d.ln_eps, st);
-    {
-      ProfScope p(s, st, 2, 2.0 * M * V * h);
-      launch_head_score(s->xn, s->wemb, tg, M, V, h, s->cus, s->sc_parts, top, scr, s->past_dev, B, S, st);
-    }
-    if (host_io) {
-      if (top) HIP_TRY(hipMemcpyAsync(sc->top_ids, top, (size_t)M * 4, hipMemcpyDeviceToHost, st));
-      if (scr) HIP_TRY(hipMemcpyAsync(sc->scores, scr, (size_t)M * 12, hipMemcpyDeviceToHost, st));
-    }
-  } else if (d.is_last && verify) {
-    // verify tail: ln_f of all M positions, the tied lm_head with the argmax epilogue over M rows (never screened),
-    // the first index of the largest logit at every position; the finalize is the pass's last kernel and advances
-    // past_dev by S for the B rows
-    // BS_STEP_VERIFY_DRAW on rows with sampler state: the head writes the logits of all M positions and the row
-    // sampler draws each of them (row_sample.hip); its pick is the pass's last kernel and advances past_dev once a row
-    const bool draws = verify_draws(s, step->flags, slot, B);
-    Epi e{};
-    e.kind = EPI_ARGMAX; e.keys = s->vf_keys; e.logits = want_logits && !host_io ? logits : nullptr; e.ldo = V;
-    float* dev_logits = nullptr;
-    if (want_logits && host_io) {
-      int rc = logits_staging(s, (size_t)M * V * 4, st, &dev_logits);
-      if (rc != BS_OK) return rc;
-      e.logits = dev_logits;
-    }
-    if (draws && !e.logits) e.logits = s->vd_logits;
-    int* tok_out = host_io ? s->vf_tok : (int*)out;
-    linear_ln(s, st, cur, 1, 0, s->lnf_g, s->lnf_b, WMat{s->wemb}, M, V, h, with_splitk(s, e), 0);
-    if (draws)
-      launch_row_sample_verify(s->vd, e.logits, V, V, slot, B, S, past_dev, tok_out, s->past_dev, st);
-    else
-      launch_argmax_finalize(s->vf_keys, M, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S, B);
-    if (host_io) {
-      HIP_TRY(hipMemcpyAsync(out, s->vf_tok, (size_t)M * 4, hipMemcpyDeviceToHost, st));
-      if (dev_logits) HIP_TRY(hipMemcpyAsync(logits, dev_logits, (size_t)M * V * 4, hipMemcpyDeviceToHost, st));
-    }
-  } else if (d.is_last) {
-    // ln_f on each row's last position, tied lm_head, token pick (greedy argmax or top-k sample)
-    const bool sample = s->top_k > 1;
-    const bool rows = rows_sampled(s, slot, B);  // excludes sample (bs_set_row_sampler / bs_set_sampling)
-    Epi e{};
-    e.kind = EPI_ARGMAX; e.keys = s->keys; e.logits = want_logits && !host_io ? logits : nullptr; e.ldo = V;
-    e.key_hi_index = sample ? 1 : 0;  // sampling ranks equal logits by the higher index (decoding.cpp:44-45)
-    float* dev_logits = nullptr;
-    if (want_logits && host_io) {
-      int rc = logits_staging(s, (size_t)B * V * 4, st, &dev_logits);
-      if (rc != BS_OK) return rc;
-      e.logits = dev_logits;
-    }
-    if ((sample || rows) && !e.logits) e.logits = s->sample_logits;
-    int* tok_out = host_io ? s->tok : (int*)out;
-    const bool screened = head_screened(s, slot, B, want_logits);
-    if (screened) {
-      // greedy, no logits, <= 2 rows: int8 screening pass, then the exact head on the few tiles that can win
-      {  // class 1 counts the bytes the screen really streams: int8 rows, scales, bound constants, rows in, hi/lo out
-        ProfScope p(s, st, 1, (double)V * h + 8.0 * V + (double)B * h * 4 + (double)B * (V / 16) * 8);
-        launch_head_screen(s->hs, cur, S, S - 1, s->lnf_g, s->lnf_b, d.ln_eps, B, V, h, s->cus, st);
+    case TAIL_SCORE: {
+      // teacher-forced scoring: ln_f of all M positions -> xn, then the tied lm_head fused with a log-softmax
+      // (head_score.hip)
+      const int* tg = sc->targets;
+      if (host_io && tg) {
+        HIP_TRY(hipMemcpyAsync(s->sc_targets, tg, (size_t)M * 4, hipMemcpyHostToDevice, st));
+        tg = s->sc_targets;
       }
-      // select + re-score + finalize stay outside class 1 (the candidate count is known on the device only);
-      // the finalize is the step's last kernel and advances past_dev by S
-      launch_head_pick(s->hs, cur, S, S - 1, s->lnf_g, s->lnf_b, d.ln_eps, s->wemb, B, V, h, e, s->cus, tok_out,
-                       s->past_dev, S, st);
-    } else {
-      linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
-      // the pick is the step's last kernel: it advances the device copy of every row's past_len by S
-      if (rows)  // rows of the call without state get the first index of their largest logit from the same kernels
-        launch_row_sample(s->rs, e.logits, V, V, slot, B, nullptr, past_dev, S, tok_out, s->past_dev, st);
-      else if (sample)
-        launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
-                           past_dev, S, tok_out, st, s->past_dev);
+      int* top = sc->top_ids ? (host_io ? s->sc_top : sc->top_ids) : nullptr;
+      float* scr = sc->scores ? (host_io ? s->sc_scores : sc->scores) : nullptr;
+      launch_layernorm(s->bf16, cur, nullptr, 1, 0, s->lnf_g, s->lnf_b, s->xn, 0, M, h, d.ln_eps, st);
+      {
+        ProfScope p(s, st, 2, 2.0 * M * V * h);
+        launch_head_score(s->xn, s->wemb, tg, M, V, h, s->cus, s->sc_parts, top, scr, s->past_dev, B, S, st);
+      }
+      if (host_io) {
+        if (top) HIP_TRY(hipMemcpyAsync(sc->top_ids, top, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+        if (scr) HIP_TRY(hipMemcpyAsync(sc->scores, scr, (size_t)M * 12, hipMemcpyDeviceToHost, st));
+      }
+      break;
+    }
+    case TAIL_VERIFY_ARGMAX:
+    case TAIL_VERIFY_DRAW: {
+      // ln_f of all M positions and the tied lm_head over M rows (never screened), then the first index of the largest
+      // logit at every position, or the row sampler's draw at each of them from the head's logits (row_sample.hip)
+      const bool draws = tail.kind == TAIL_VERIFY_DRAW;
+      Epi e{};
+      e.kind = EPI_ARGMAX; e.keys = s->vf_keys; e.ldo = V;
+      if ((rc = tail_logits(s, tail, step, logits, draws ? s->vd_logits : nullptr, st, &e.logits, &staged)) != BS_OK) return rc;
+      int* tok_out = host_io ? s->vf_tok : (int*)out;
+      linear_ln(s, st, cur, 1, 0, s->lnf_g, s->lnf_b, WMat{s->wemb}, M, V, h, with_splitk(s, e), 0);
+      if (draws)
+        launch_row_sample_verify(s->vd, e.logits, V, V, slot, B, S, past_dev, tok_out, s->past_dev, st);
       else
-        launch_argmax_finalize(s->keys, B, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S);
+        launch_argmax_finalize(s->vf_keys, M, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S, B);
+      return tail_copy_out(tail, step, s->vf_tok, out, staged, logits, st);
     }
-    if (host_io) {
-      HIP_TRY(hipMemcpyAsync(out, s->tok, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-      if (dev_logits) HIP_TRY(hipMemcpyAsync(logits, dev_logits, (size_t)B * V * 4, hipMemcpyDeviceToHost, st));
+    case TAIL_SCREENED:
+    case TAIL_GREEDY:
+    case TAIL_TOPK:
+    case TAIL_ROWS: {
+      // ln_f on each row's last position, tied lm_head, token pick
+      const bool reads_logits = tail.kind == TAIL_TOPK || tail.kind == TAIL_ROWS;
+      Epi e{};
+      e.kind = EPI_ARGMAX; e.keys = s->keys; e.ldo = V;
+      e.key_hi_index = tail.kind == TAIL_TOPK ? 1 : 0;  // sampling ranks equal logits by the higher index (decoding.cpp:44-45)
+      if ((rc = tail_logits(s, tail, step, logits, reads_logits ? s->sample_logits : nullptr, st, &e.logits, &staged)) != BS_OK)
+        return rc;
+      int* tok_out = host_io ? s->tok : (int*)out;
+      if (tail.kind == TAIL_SCREENED) {
+        // int8 screening pass, then the exact head on the few tiles that can win
+        {  // class 1 counts the bytes the screen really streams: int8 rows, scales, bound constants, rows in, hi/lo out
+          ProfScope p(s, st, 1, (double)V * h + 8.0 * V + (double)B * h * 4 + (double)B * (V / 16) * 8);
+          launch_head_screen(s->hs, cur, S, S - 1, s->lnf_g, s->lnf_b, d.ln_eps, B, V, h, s->cus, st);
+        }
+        // select + re-score + finalize stay outside class 1 (the candidate count is known on the device only)
+        launch_head_pick(s->hs, cur, S, S - 1, s->lnf_g, s->lnf_b, d.ln_eps, s->wemb, B, V, h, e, s->cus, tok_out,
+                         s->past_dev, S, st);
+      } else {
+        linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
+        if (tail.kind == TAIL_ROWS)  // rows of the call without state get the first index of their largest logit
+          launch_row_sample(s->rs, e.logits, V, V, slot, B, nullptr, past_dev, S, tok_out, s->past_dev, st);
+        else if (tail.kind == TAIL_TOPK)
+          launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
+                             past_dev, S, tok_out, st, s->past_dev);
+        else
+          launch_argmax_finalize(s->keys, B, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S);
+      }
+      return tail_copy_out(tail, step, s->tok, out, staged, logits, st);
     }
-  } else if (host_io) {
-    HIP_TRY(hipMemcpyAsync(out, cur, (size_t)M * h * 4, hipMemcpyDeviceToHost, st));
-  } else if (s->L == 0) {
-    HIP_TRY(hipMemcpyAsync(out, cur, (size_t)M * h * 4, hipMemcpyDeviceToDevice, st));
   }
   return BS_OK;
 }
@@ -1524,6 +1436,31 @@ extern "C" int bs_head_slice(bs_stage* s, const void* xn, int32_t B, const uint6
   return BS_OK;
 }
 
+// ---- the graph cache: captured decode steps and verify passes by GraphKey, at most 64
+static hipGraphExec_t find_graph(const bs_stage* s, const GraphKey& key) {
+  for (const auto& g : s->graphs)
+    if (g.first == key) return g.second;
+  return nullptr;
+}
+
+static int insert_graph(bs_stage* s, const GraphKey& key, hipGraphExec_t exec) {
+  if (s->graphs.size() >= 64) {
+    HIP_TRY(hipStreamSynchronize(key.st));  // the evicted (oldest) graph may still be replaying on this stream
+    hipGraphExecDestroy(s->graphs.front().second);
+    s->graphs.erase(s->graphs.begin());
+  }
+  s->graphs.push_back({key, exec});
+  return BS_OK;
+}
+
+// A setter changed what the captured tails hold (the pick, the screening, graphs off): wait for the device, drop all.
+static int drop_graphs(bs_stage* s) {
+  HIP_TRY(hipDeviceSynchronize());
+  for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
+  s->graphs.clear();
+  return BS_OK;
+}
+
 extern "C" int bs_set_sampling(bs_stage* s, int32_t top_k, float temperature, uint64_t seed) {
   if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
   if (top_k > 16) return fail(BS_ERR_UNSUPPORTED, "top_k must be <= 16");
@@ -1534,47 +1471,42 @@ extern "C" int bs_set_sampling(bs_stage* s, int32_t top_k, float temperature, ui
   HIP_TRY(hipSetDevice(s->d.device));
   if (top_k > 1 && !s->sample_logits) {
     HIP_TRY(hipStreamSynchronize(s->own));
-    if (hipMalloc((void**)&s->sample_logits, (size_t)s->d.max_batch * s->d.vocab * 4) != hipSuccess)
+    if (!owned_alloc(s, (size_t)s->d.max_batch * s->d.vocab * 4, false, (void**)&s->sample_logits))
       return fail(BS_ERR_OOM, "sampling logits allocation failed");
   }
   s->top_k = top_k < 1 ? 1 : top_k;
   s->temperature = top_k > 1 ? temperature : 1.f;
   s->sample_seed = seed;
-  // captured decode graphs hold the old pick as kernel arguments
-  HIP_TRY(hipDeviceSynchronize());
-  for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
-  s->graphs.clear();
-  return BS_OK;
+  return drop_graphs(s);  // they hold the old pick as kernel arguments
 }
 
 // ---- per-row sampling (row_sample.hip)
 static_assert(sizeof(bs_row_draw) == sizeof(RowDrawDev) && sizeof(bs_row_draw) == 40, "bs_row_draw layout");
 
-// The table, histograms and read-outs, and the [max_batch][V] logits buffer if bs_set_sampling has not made it.
+// Sampler scratch (row_sample.hip lays it out): one allocation, zeroed by Carver's rule; `what` names it in errors.
+static int sampler_scratch(bs_stage* s, size_t bytes, const std::string& what, char** base) {
+  Carver c;
+  c.piece(base, bytes);
+  const int rc = c.alloc(s->own);
+  if (rc == Carver::NO_MEMORY) return fail(BS_ERR_OOM, what + " allocation failed (" + std::to_string(bytes) + " B)");
+  if (rc == Carver::NOT_ZEROED) return fail(BS_ERR_DEVICE, what + " memset");
+  return BS_OK;
+}
+
+// The table, histograms and read-outs, and the [max_batch][V] logits buffer if bs_set_sampling has not made it
+// (then it counts as workspace, else not).
 static int row_sampler_buffers(bs_stage* s) {
-  if (s->rs_base) return BS_OK;
+  if (s->rs.table) return BS_OK;
   size_t off[6];
   const size_t bytes = row_sample_bytes(s->d.max_batch, off);
   char* base = nullptr;
-  if (hipMalloc((void**)&base, bytes) != hipSuccess)
-    return fail(BS_ERR_OOM, "row sampler buffers allocation failed (" + std::to_string(bytes) + " B)");
-  // zeroed before any stream can write the table (a plain hipMemset of device memory may still be running when it
-  // returns, and the caller's stream is not ordered behind it)
-  if (hipMemsetAsync(base, 0, bytes, s->own) != hipSuccess || hipStreamSynchronize(s->own) != hipSuccess) {
+  int rc = sampler_scratch(s, bytes, "row sampler buffers", &base);
+  if (rc != BS_OK) return rc;
+  if (!s->sample_logits && !owned_alloc(s, (size_t)s->d.max_batch * s->d.vocab * 4, true, (void**)&s->sample_logits)) {
     hipFree(base);
-    return fail(BS_ERR_DEVICE, "row sampler buffers memset");
+    return fail(BS_ERR_OOM, "sampling logits allocation failed");
   }
-  size_t lb = 0;
-  if (!s->sample_logits) {
-    lb = (size_t)s->d.max_batch * s->d.vocab * 4;
-    if (hipMalloc((void**)&s->sample_logits, lb) != hipSuccess) {
-      s->sample_logits = nullptr;
-      hipFree(base);
-      return fail(BS_ERR_OOM, "sampling logits allocation failed");
-    }
-  }
-  s->rs_base = base;
-  s->rs_bytes = bytes + lb;
+  s->owned.push_back({base, bytes});
   s->rs = row_sample_bufs(base, off);
   s->rs_host.assign(s->d.max_batch, RowSamplerDev{});
   return BS_OK;
@@ -1600,7 +1532,7 @@ extern "C" int bs_set_row_sampler(bs_stage* s, int32_t slot, int32_t count, cons
     if (!(p.temperature > 0.f) || std::isinf(p.temperature)) return fail(BS_ERR_INVALID, "temperature must be positive and finite");
     rows[i] = RowSamplerDev{p.top_k, p.top_p, p.temperature, 1, p.seed};
   }
-  if (!params && !s->rs_base) return BS_OK;  // nothing was ever set
+  if (!params && !s->rs.table) return BS_OK;  // nothing was ever set
   HIP_TRY(hipSetDevice(s->d.device));
   if ((rc = row_sampler_buffers(s)) != BS_OK) return rc;
   launch_row_table(s->rs, slot, rows.data(), count, stream ? (hipStream_t)stream : s->own);
@@ -1651,7 +1583,7 @@ extern "C" int bs_sample_logits(bs_stage* s, int32_t slot, int32_t batch, const 
 extern "C" int bs_read_row_draw(bs_stage* s, int32_t slot, bs_row_draw* out) {
   if (!s || !out) return fail(BS_ERR_INVALID, "stage/out is NULL");
   if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot out of range");
-  if (!s->rs_base) return fail(BS_ERR_STATE, "the stage never ran the per-row sampler");
+  if (!s->rs.table) return fail(BS_ERR_STATE, "the stage never ran the per-row sampler");
   HIP_TRY(hipSetDevice(s->d.device));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, s->rs.draw + slot, sizeof(*out), hipMemcpyDeviceToHost));
@@ -1659,29 +1591,21 @@ extern "C" int bs_read_row_draw(bs_stage* s, int32_t slot, bs_row_draw* out) {
 }
 
 // The scratch of a verify-draw pass (first use) and, when the pass has no other device logits to write, its own
-// logits buffer (first such use).  Zeroed on the stage's own stream and synchronised, like the per-row scratch.
+// logits buffer (first such use).
 static int verify_draw_buffers(bs_stage* s, bool need_logits) {
-  if (!s->vd_base) {
+  if (!s->vd.draw) {
     size_t off[7];
     const size_t bytes = row_sample_verify_bytes(off);
     char* base = nullptr;
-    if (hipMalloc((void**)&base, bytes) != hipSuccess)
-      return fail(BS_ERR_OOM, "verify-draw sampler scratch allocation failed (" + std::to_string(bytes) + " B)");
-    if (hipMemsetAsync(base, 0, bytes, s->own) != hipSuccess || hipStreamSynchronize(s->own) != hipSuccess) {
-      hipFree(base);
-      return fail(BS_ERR_DEVICE, "verify-draw sampler scratch memset");
-    }
-    s->vd_base = base;
-    s->vd_bytes += bytes;
+    int rc = sampler_scratch(s, bytes, "verify-draw sampler scratch", &base);
+    if (rc != BS_OK) return rc;
+    s->owned.push_back({base, bytes});
     s->vd = row_sample_verify_bufs(s->rs, base, off);
   }
   if (need_logits && !s->vd_logits) {
     const size_t lb = (size_t)std::max(s->d.max_batch, kVerifyMaxTokens) * s->d.vocab * 4;
-    if (hipMalloc((void**)&s->vd_logits, lb) != hipSuccess) {
-      s->vd_logits = nullptr;
+    if (!owned_alloc(s, lb, true, (void**)&s->vd_logits))
       return fail(BS_ERR_OOM, "verify-draw logits allocation failed (" + std::to_string(lb) + " B)");
-    }
-    s->vd_bytes += lb;
   }
   return BS_OK;
 }
@@ -1701,23 +1625,18 @@ extern "C" int bs_read_verify_draw(bs_stage* s, int32_t slot, int32_t t, bs_row_
 extern "C" int bs_set_graphs(bs_stage* s, int32_t on) {
   if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
   HIP_TRY(hipSetDevice(s->d.device));
-  HIP_TRY(hipDeviceSynchronize());
-  for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
-  s->graphs.clear();
-  s->graphs_on = on ? 1 : 0;
-  return BS_OK;
+  int rc = drop_graphs(s);
+  if (rc == BS_OK) s->graphs_on = on ? 1 : 0;
+  return rc;
 }
 
 extern "C" int bs_set_head_screen(bs_stage* s, int32_t on) {
   if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
-  if (on && !s->hs_base) return fail(BS_ERR_STATE, "stage holds no head shadow copy (bf16 last stage with the whole lm_head)");
+  if (on && !s->hs.Q) return fail(BS_ERR_STATE, "stage holds no head shadow copy (bf16 last stage with the whole lm_head)");
   HIP_TRY(hipSetDevice(s->d.device));
-  // captured decode graphs hold the old tail
-  HIP_TRY(hipDeviceSynchronize());
-  for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
-  s->graphs.clear();
-  s->hs_on = on ? 1 : 0;
-  return BS_OK;
+  int rc = drop_graphs(s);  // they hold the old tail
+  if (rc == BS_OK) s->hs_on = on ? 1 : 0;
+  return rc;
 }
 
 extern "C" int bs_read_head_screen(bs_stage* s, int32_t row, float* hilo, float* lstar, int32_t* list, int32_t* count) {
@@ -1786,26 +1705,21 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   BS_TRACE("B=%d S=%d slot=%d flags=%u stream=%p hipSetDevice", B, S, slot, (unsigned)step->flags, stream);
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t st = stream ? (hipStream_t)stream : s->own;
-  if (verify && !s->vf_base) {  // first verify call: split partials of the attention, keys and ids of every position
-    s->vf_stride = attention_verify_split_stride(d.n_head, s->max_chunks);
-    const size_t accf = (size_t)kVerifyMaxTokens * d.n_head * s->vf_stride * s->hd;
-    const size_t mlf = (size_t)kVerifyMaxTokens * d.n_head * s->vf_stride * 2;
-    const size_t sizes[4] = {accf * 4, mlf * 4, d.is_last ? (size_t)kVerifyMaxTokens * (d.vocab / 16) * 8 : 0,
-                             (size_t)kVerifyMaxTokens * 4};
-    size_t vo[4], off = 0;
-    for (int i = 0; i < 4; i++) { vo[i] = off; off = align_up(off + sizes[i], 256); }
-    if (hipMalloc((void**)&s->vf_base, off) != hipSuccess) {
-      s->vf_base = nullptr;
-      return fail(BS_ERR_OOM, "verify buffers allocation failed (" + std::to_string(off) + " B)");
-    }
-    s->vf_bytes = off;
-    s->vf_acc = (float*)(s->vf_base + vo[0]);
-    s->vf_ml = (float*)(s->vf_base + vo[1]);
-    s->vf_keys = (unsigned long long*)(s->vf_base + vo[2]);
-    s->vf_tok = (int*)(s->vf_base + vo[3]);
+  // ---- what the pass ends in, and the buffers its attention and that tail need, made before any capture
+  const Tail tail = plan_tail(s, step, sc != nullptr);
+  if (verify && !s->vf_acc) {  // first verify call: split partials of the attention, keys and ids of every position
+    const int stride = attention_verify_split_stride(d.n_head, s->max_chunks);
+    Carver c;
+    c.piece(&s->vf_acc, (size_t)kVerifyMaxTokens * d.n_head * stride * s->hd * 4);
+    c.piece(&s->vf_ml, (size_t)kVerifyMaxTokens * d.n_head * stride * 2 * 4);
+    c.piece(&s->vf_keys, d.is_last ? (size_t)kVerifyMaxTokens * (d.vocab / 16) * 8 : 0);
+    c.piece(&s->vf_tok, (size_t)kVerifyMaxTokens * 4);
+    if (c.alloc() != Carver::OK)
+      return fail(BS_ERR_OOM, "verify buffers allocation failed (" + std::to_string(c.total) + " B)");
+    s->owned.push_back({c.base, c.total});
+    s->vf_stride = stride;
   }
-  const bool draws = verify_draws(s, step->flags, slot, B);
-  if (draws) {
+  if (tail.kind == TAIL_VERIFY_DRAW) {
     int rc = verify_draw_buffers(s, !want_logits);  // host-I/O logits go through the logits staging
     if (rc != BS_OK) return rc;
   }
@@ -1819,53 +1733,42 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
                             std::equal(pasts.begin(), pasts.end(), s->past_next.begin());
   s->past_next_valid = false;  // until this forward is enqueued
   const bool graph = (S == 1 || verify) && !host_io && s->prof.cls == 0 && s->graphs_on && !sc;  // scoring is always eager
-  if (graph) {
-    GraphKey key{B, S, slot, step->flags, rows_sampled(s, slot, B) ? 1 : 0, in, out, logits, st};
-    hipGraphExec_t exec = nullptr;
-    for (auto& g : s->graphs)
-      if (g.first == key) { exec = g.second; break; }
-    if (!exec) {
-      hipGraph_t gr = nullptr;
-      BS_TRACE("hipStreamBeginCapture");
-      HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-      BS_TRACE("enqueue_forward (capturing)");
-      int rc = enqueue_forward(s, step, in, out, logits, st, s->past_dev, pasts);
-      BS_TRACE("hipStreamEndCapture");
-      hipError_t ce = hipStreamEndCapture(st, &gr);
-      if (rc != BS_OK) { if (gr) hipGraphDestroy(gr); return rc; }
-      if (ce != hipSuccess) return fail(BS_ERR_DEVICE, std::string("graph capture: ") + hipGetErrorString(ce));
-      BS_TRACE("hipGraphInstantiate");
-      hipError_t ie = hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0);
-      BS_TRACE("hipGraphDestroy");
-      hipGraphDestroy(gr);
-      if (ie != hipSuccess) return fail(BS_ERR_DEVICE, std::string("graph instantiate: ") + hipGetErrorString(ie));
-      if (s->graphs.size() >= 64) {
-        HIP_TRY(hipStreamSynchronize(st));  // the evicted graph may still be replaying on this stream
-        hipGraphExecDestroy(s->graphs.front().second);
-        s->graphs.erase(s->graphs.begin());
-      }
-      s->graphs.push_back({key, exec});
-    }
-    if (!past_matches) {
-      BS_TRACE("set_past launch");
-      launch_set_past(s->past_dev, pasts.data(), B, st);
-    }
+  hipGraphExec_t exec = nullptr;
+  const GraphKey key{B, S, slot, step->flags, tail.kind, in, out, logits, st};
+  if (graph && !(exec = find_graph(s, key))) {
+    hipGraph_t gr = nullptr;
+    BS_TRACE("hipStreamBeginCapture");
+    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+    BS_TRACE("enqueue_forward (capturing)");
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts);
+    BS_TRACE("hipStreamEndCapture");
+    hipError_t ce = hipStreamEndCapture(st, &gr);
+    if (rc != BS_OK) { if (gr) hipGraphDestroy(gr); return rc; }
+    if (ce != hipSuccess) return fail(BS_ERR_DEVICE, std::string("graph capture: ") + hipGetErrorString(ce));
+    BS_TRACE("hipGraphInstantiate");
+    hipError_t ie = hipGraphInstantiate(&exec, gr, nullptr, nullptr, 0);
+    BS_TRACE("hipGraphDestroy");
+    hipGraphDestroy(gr);
+    if (ie != hipSuccess) return fail(BS_ERR_DEVICE, std::string("graph instantiate: ") + hipGetErrorString(ie));
+    if ((rc = insert_graph(s, key, exec)) != BS_OK) return rc;
+  }
+  if (!past_matches) {
+    BS_TRACE("set_past launch");
+    launch_set_past(s->past_dev, pasts.data(), B, st);
+  }
+  if (exec) {
     BS_TRACE("hipGraphLaunch");
     HIP_TRY(hipGraphLaunch(exec, st));
   } else {
-    if (!past_matches) {
-      BS_TRACE("set_past launch");
-      launch_set_past(s->past_dev, pasts.data(), B, st);
-    }
     BS_TRACE("enqueue_forward (eager)");
-    int rc = enqueue_forward(s, step, in, out, logits, st, s->past_dev, pasts, sc);
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, sc);
     if (rc != BS_OK) return rc;
   }
   BS_TRACE("hipGetLastError");
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
-  s->hs_last_rows = !sc && !verify && head_screened(s, slot, B, want_logits) ? B : 0;
-  if (draws) { s->vd_last_slot = slot; s->vd_last_B = B; s->vd_last_S = S; }
+  s->hs_last_rows = tail.kind == TAIL_SCREENED ? B : 0;
+  if (tail.kind == TAIL_VERIFY_DRAW) { s->vd_last_slot = slot; s->vd_last_B = B; s->vd_last_S = S; }
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)
     s->past_next.assign(pasts.begin(), pasts.end());
     for (int& p : s->past_next) p += S;
@@ -1894,24 +1797,20 @@ extern "C" int bs_forward_score(bs_stage* s, const bs_step* step, const void* in
   if (step->flags & BS_STEP_LOGITS) return fail(BS_ERR_INVALID, "BS_STEP_LOGITS is not valid for a scoring pass");
   if (!top_ids && !scores) return fail(BS_ERR_INVALID, "top_ids and scores are both NULL");
   HIP_TRY(hipSetDevice(d.device));
-  if (!s->sc_base) {  // first scoring call: partials for the largest pass + host-I/O staging
+  if (!s->sc_parts) {  // first scoring call: partials for the largest pass + host-I/O staging
     if (s->cus <= 0) HIP_TRY(hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, d.device));
     const size_t T = d.max_tokens;
     size_t pb = 0;
     for (size_t m = 128; m < T + 128; m += 128)  // the splits shrink as the row tiles grow
       pb = std::max(pb, head_score_partial_bytes((int)std::min(m, T), d.vocab, s->cus));
-    const size_t sizes[4] = {pb, T * 4, T * 4, T * 12};
-    size_t so[4], off = 0;
-    for (int i = 0; i < 4; i++) { so[i] = off; off = align_up(off + sizes[i], 256); }
-    if (hipMalloc((void**)&s->sc_base, off) != hipSuccess) {
-      s->sc_base = nullptr;
-      return fail(BS_ERR_OOM, "scoring buffers allocation failed (" + std::to_string(off) + " B)");
-    }
-    s->sc_bytes = off;
-    s->sc_parts = s->sc_base + so[0];
-    s->sc_targets = (int*)(s->sc_base + so[1]);
-    s->sc_top = (int*)(s->sc_base + so[2]);
-    s->sc_scores = (float*)(s->sc_base + so[3]);
+    Carver c;
+    c.piece(&s->sc_parts, pb);
+    c.piece(&s->sc_targets, T * 4);
+    c.piece(&s->sc_top, T * 4);
+    c.piece(&s->sc_scores, T * 12);
+    if (c.alloc() != Carver::OK)
+      return fail(BS_ERR_OOM, "scoring buffers allocation failed (" + std::to_string(c.total) + " B)");
+    s->owned.push_back({c.base, c.total});
   }
   const ScoreIO sc{targets, top_ids, scores};
   return forward_impl(s, step, in, nullptr, nullptr, &sc, stream);
