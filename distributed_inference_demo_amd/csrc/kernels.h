@@ -149,6 +149,20 @@ bool kv_fork_supported(int npos, size_t pos_bytes);
 void launch_kv_fork(void* base, int chunk_bytes, int n_lw, int n_head, int max_batch, int max_ctx, size_t pos_bytes,
                     int src_slot, int dst_slot, int count, int npos, int cus, hipStream_t s);
 
+// ---- Top-k log-prob tail (bs_forward_topk; beam_topk.hip) ----
+// From fp32 logits [B][ld] (V columns each, ld % 4 == 0, 16-byte aligned): per row the k <= kTopkMaxK best token ids
+// (larger logit first, the lower index first on equal logits) -> ids [B][k], their log-probabilities -> logprobs
+// [B][k] and the row's log-sum-exp -> lse [B] (optional).  Two launches; the partials are one record per (row, slice
+// of kTopkSlice logits): pmax, psum [B][topk_slices(V)] and pkeys [B][topk_slices(V)][kTopkMaxK].  The second launch
+// does past_adv[b] += seq (optional): the pass's last kernel.  V <= kTopkSlice * kTopkMaxSlices.
+constexpr int kTopkMaxK = 16;
+constexpr int kTopkSlice = 2048;
+constexpr int kTopkMaxSlices = 1024;
+int topk_slices(int V);
+void launch_topk_logprobs(const float* logits, int ld, int V, int B, int k, float* pmax, float* psum,
+                          unsigned long long* pkeys, int* ids, float* logprobs, float* lse, int* past_adv, int seq,
+                          hipStream_t s);
+
 // Split-attention partials as the consumer reads them (attn_merge.h).
 struct AttnParts {
   const float* acc;  // AttnArgs::part_acc

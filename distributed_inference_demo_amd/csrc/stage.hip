@@ -11,11 +11,11 @@
 //   errors and tracing; Carver (one device allocation cut into aligned pieces); bs_stage and the allocations it owns
 //   validate, bs_stage_weight_count (the weight table is stage_weights.h), checkpoint lookup
 //   init_stage: weight arena + binding, the three weight sources, head screening, KV cache, workspace
-//   bs_stage_info, bs_read_weights, bs_read_kv, bs_reset_kv, bs_fork_kv
+//   bs_stage_info, bs_read_weights, bs_read_kv, bs_reset_kv, bs_fork_kv, bs_copy_kv
 //   profiling, bs_stream_delay, the HBM and MFMA probes
 //   the forward: linear / linear_ln, Tail (which tail a pass ends in, decided once), enqueue_forward
 //   head slices, sampling setters, the per-row sampler and verify-draw buffers, the graph cache
-//   forward_impl (checks, lazy buffers, capture or eager enqueue), bs_forward, bs_forward_score
+//   forward_impl (checks, lazy buffers, capture or eager enqueue), bs_forward, bs_forward_score, bs_forward_topk
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -81,6 +81,7 @@ enum TailKind {
   TAIL_GREEDY,         // full head, argmax
   TAIL_TOPK,           // full head, bs_set_sampling's seeded top-k
   TAIL_ROWS,           // full head, per-row sampler (a row of the call holds sampler state)
+  TAIL_TOPK_LOGPROBS,  // bs_forward_topk: full head with its logits written, the k best ids and log-probs of each row
 };
 struct Tail {
   TailKind kind = TAIL_NONE;
@@ -96,9 +97,12 @@ struct GraphKey {
   void* out;
   float* logits;
   hipStream_t st;
+  int k = 0;  // TAIL_TOPK_LOGPROBS: candidates per row, and where the log-probs and the lse go (out = the ids)
+  const void* logprobs = nullptr;
+  const void* lse = nullptr;
   bool operator==(const GraphKey& o) const {
     return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && tail == o.tail && in == o.in &&
-           out == o.out && logits == o.logits && st == o.st;
+           out == o.out && logits == o.logits && st == o.st && k == o.k && logprobs == o.logprobs && lse == o.lse;
   }
 };
 
@@ -267,6 +271,14 @@ struct bs_stage {
   RowSampleBufs vd{};
   float* vd_logits = nullptr;
   int vd_last_slot = 0, vd_last_B = 0, vd_last_S = 0;  // B == 0: no verify-draw pass ran
+  // bs_forward_topk (beam_topk.hip): the per-(row, slice) partials and the host-I/O staging of ids / logprobs / lse,
+  // one allocation made by the first call (tk_pmax null: never)
+  float* tk_pmax = nullptr;             // [max_batch][topk_slices(V)]
+  float* tk_psum = nullptr;             // [max_batch][topk_slices(V)]
+  unsigned long long* tk_pkeys = nullptr;  // [max_batch][topk_slices(V)][kTopkMaxK]
+  int* tk_ids = nullptr;                // [max_batch][kTopkMaxK]
+  float* tk_lp = nullptr;               // [max_batch][kTopkMaxK]
+  float* tk_lse = nullptr;              // [max_batch]
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -274,6 +286,15 @@ struct ScoreIO {
   const int32_t* targets;
   int32_t* top_ids;
   float* scores;
+};
+
+// What a top-k pass (bs_forward_topk) writes instead of bs_forward's out; logits null: none are returned.
+struct TopkIO {
+  int k;
+  int32_t* ids;
+  float* logprobs;
+  float* lse;
+  float* logits;
 };
 
 // Allocate `bytes` into the list the stage owns (freed with the stage), counted as workspace or not.
@@ -865,6 +886,48 @@ extern "C" int bs_fork_kv(bs_stage* s, int32_t src_slot, int32_t dst_slot, int32
   return BS_OK;
 }
 
+// KV row pair copy: bs_fork_kv's contract for a list of (source row -> destination row) pairs, as fork launches
+// (kv_fork.hip) -- one per run of pairs that share a source and have consecutive destinations (one more each for an
+// int8 cache's scales).  A one-launch pair-list variant of the kernel measured slower than the fork launches of the
+// same pairs at 5 of 12 points and was dropped.  The no-alias checks leave the launches
+// without an ordering hazard among themselves.
+extern "C" int bs_copy_kv(bs_stage* s, const int32_t* src_slots, const int32_t* dst_slots, int32_t count, int32_t npos,
+                          void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  const int mb = s->d.max_batch;
+  if (count < 0 || count > 32) return fail(BS_ERR_INVALID, "count must be in [0, 32]");
+  if (count > 0 && (!src_slots || !dst_slots)) return fail(BS_ERR_INVALID, "slot lists are NULL");
+  if (npos < 0 || npos > s->d.max_ctx) return fail(BS_ERR_INVALID, "npos outside [0, max_ctx]");
+  for (int i = 0; i < count; i++) {
+    if (src_slots[i] < 0 || src_slots[i] >= mb || dst_slots[i] < 0 || dst_slots[i] >= mb)
+      return fail(BS_ERR_INVALID, "slot outside max_batch");
+    for (int j = 0; j < count; j++) {
+      if (dst_slots[i] == src_slots[j]) return fail(BS_ERR_INVALID, "a destination row is also a source row");
+      if (j < i && dst_slots[i] == dst_slots[j]) return fail(BS_ERR_INVALID, "a destination row appears twice");
+    }
+  }
+  if (!count || !npos || s->L <= 0) return BS_OK;
+  const size_t pos_bytes = (size_t)s->hd * (s->kv8 ? 1 : s->esz);  // a multiple of 16 (head_dim % 8, % 16 for int8)
+  if (!kv_fork_supported(npos, pos_bytes)) return fail(BS_ERR_UNSUPPORTED, "npos * head_dim too large for the copy kernel");
+  HIP_TRY(hipSetDevice(s->d.device));
+  if (s->cus <= 0 && hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, s->d.device) != hipSuccess) {
+    (void)hipGetLastError();
+    s->cus = 0;  // the launch falls back to 256
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  for (int i = 0; i < count;) {
+    int n = 1;  // pairs i .. i + n - 1: one source, destinations dst, dst + 1, ...
+    while (i + n < count && src_slots[i + n] == src_slots[i] && dst_slots[i + n] == dst_slots[i] + n) n++;
+    launch_kv_fork(s->kv, 16, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, pos_bytes, src_slots[i], dst_slots[i], n, npos, s->cus, st);
+    if (s->kv8)  // scale segments start on 4-byte boundaries only
+      launch_kv_fork(s->kv_scales, 4, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, 4, src_slots[i], dst_slots[i], n, npos, s->cus, st);
+    i += n;
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kv copy: ") + hipGetErrorString(err));
+  return BS_OK;
+}
+
 // ---- profiling
 extern "C" int bs_profile_enable(bs_stage* s, int32_t cls) {
   if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
@@ -1132,11 +1195,12 @@ static bool rows_sampled(const bs_stage* s, int slot, int B) {
 }
 
 // Which tail this pass ends in (scoring: a bs_forward_score pass).  forward_impl has checked the step against the stage.
-static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring) {
+static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring, bool topk = false) {
   const int B = step->batch, M = B * step->seq, V = s->d.vocab;
   if (!s->d.is_last) return Tail{};
   if (s->n_labels) return Tail{TAIL_CLASSIFY, B, s->n_labels};
   if (scoring) return Tail{TAIL_SCORE, M, V};
+  if (topk) return Tail{TAIL_TOPK_LOGPROBS, B, V};  // bs_forward_topk has excluded sampler state of either kind
   const bool rows = rows_sampled(s, step->slot, B);  // excludes top_k > 1 (bs_set_row_sampler / bs_set_sampling)
   if (step->flags & BS_STEP_VERIFY)
     return Tail{rows && (step->flags & BS_STEP_VERIFY_DRAW) ? TAIL_VERIFY_DRAW : TAIL_VERIFY_ARGMAX, M, V};
@@ -1193,10 +1257,11 @@ static int tail_copy_out(const Tail& t, const bs_step* step, const int* tok, voi
 
 // Enqueue one forward on `st`.  The kernels read each row's past_len from past_dev (device [B],
 // written ahead of the forward or of the graph replay); `pasts` is the host copy (profiling bytes).
-// tail: what forward_impl planned; sc: what a TAIL_SCORE reads and writes (bs_forward_score).
+// tail: what forward_impl planned; sc: what a TAIL_SCORE reads and writes (bs_forward_score); tk: what a
+// TAIL_TOPK_LOGPROBS writes (bs_forward_topk).
 static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, const void* in, void* out, float* logits,
                            hipStream_t st, const int* past_dev, const std::vector<int>& pasts,
-                           const ScoreIO* sc = nullptr) {
+                           const ScoreIO* sc = nullptr, const TopkIO* tk = nullptr) {
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot, past = pasts[0];
   double ctx_sum = 0.0;
@@ -1401,6 +1466,29 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
           launch_argmax_finalize(s->keys, B, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S);
       }
       return tail_copy_out(tail, step, s->tok, out, staged, logits, st);
+    }
+    case TAIL_TOPK_LOGPROBS: {
+      // ln_f on each row's last position, the full head with its logits written (the caller's buffer, with host I/O
+      // the staging, else the sampling-logits buffer), then the k best and the log-sum-exp from them (beam_topk.hip)
+      const int k = tk->k;
+      float* dev_logits = s->sample_logits;
+      if (tk->logits) {
+        dev_logits = tk->logits;
+        if (host_io && (rc = logits_staging(s, (size_t)B * V * 4, st, &dev_logits)) != BS_OK) return rc;
+      }
+      Epi e{};
+      e.kind = EPI_ARGMAX; e.keys = s->keys; e.ldo = V; e.logits = dev_logits;
+      linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
+      launch_topk_logprobs(dev_logits, V, V, B, k, s->tk_pmax, s->tk_psum, s->tk_pkeys, host_io ? s->tk_ids : tk->ids,
+                           host_io ? s->tk_lp : tk->logprobs, tk->lse ? (host_io ? s->tk_lse : tk->lse) : nullptr,
+                           s->past_dev, S, st);
+      if (host_io) {
+        HIP_TRY(hipMemcpyAsync(tk->ids, s->tk_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(tk->logprobs, s->tk_lp, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
+        if (tk->lse) HIP_TRY(hipMemcpyAsync(tk->lse, s->tk_lse, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        if (tk->logits) HIP_TRY(hipMemcpyAsync(tk->logits, dev_logits, (size_t)B * V * 4, hipMemcpyDeviceToHost, st));
+      }
+      break;
     }
   }
   return BS_OK;
@@ -1653,10 +1741,32 @@ extern "C" int bs_read_head_screen(bs_stage* s, int32_t row, float* hilo, float*
   return BS_OK;
 }
 
+// The buffers of a top-k pass (first use): slice partials + host-I/O staging, and the [max_batch][vocab] logits buffer
+// if no sampler has made it (then it counts as workspace, as in row_sampler_buffers).
+static int topk_buffers(bs_stage* s) {
+  if (s->tk_pmax) return BS_OK;
+  const size_t mb = s->d.max_batch, ns = topk_slices(s->d.vocab);
+  Carver c;
+  c.piece(&s->tk_pmax, mb * ns * 4);
+  c.piece(&s->tk_psum, mb * ns * 4);
+  c.piece(&s->tk_pkeys, mb * ns * kTopkMaxK * 8);
+  c.piece(&s->tk_ids, mb * kTopkMaxK * 4);
+  c.piece(&s->tk_lp, mb * kTopkMaxK * 4);
+  c.piece(&s->tk_lse, mb * 4);
+  if (c.alloc() != Carver::OK) return fail(BS_ERR_OOM, "top-k buffers allocation failed (" + std::to_string(c.total) + " B)");
+  if (!s->sample_logits && !owned_alloc(s, mb * s->d.vocab * 4, true, (void**)&s->sample_logits)) {
+    hipFree(c.base);
+    s->tk_pmax = nullptr;
+    return fail(BS_ERR_OOM, "top-k logits allocation failed");
+  }
+  s->owned.push_back({c.base, c.total});
+  return BS_OK;
+}
+
 // bs_forward and bs_forward_score (sc non-null): argument checks, the rows' positions on the device, the enqueue
 // (captured or eager) and the bookkeeping of what the pass's last kernel left in past_dev.
 static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, const ScoreIO* sc,
-                        void* stream) {
+                        void* stream, const TopkIO* tk = nullptr) {
   if (!s || !step) return fail(BS_ERR_INVALID, "stage/step is NULL");
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot;
@@ -1693,7 +1803,8 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     if (!draw && rows_sampled(s, slot, B))
       return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a row that holds sampler state (BS_STEP_VERIFY_DRAW draws from it)");
   }
-  if (!in || (!out && !sc)) return fail(BS_ERR_INVALID, "in/out is NULL");
+  if (!in || (!out && !sc && !tk)) return fail(BS_ERR_INVALID, "in/out is NULL");
+  if (tk && rows_sampled(s, slot, B)) return fail(BS_ERR_STATE, "bs_forward_topk on a row that holds sampler state");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   if (want_logits && (!d.is_last || !logits)) return fail(BS_ERR_INVALID, "logits requested on a non-last stage or NULL");
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
@@ -1706,7 +1817,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   HIP_TRY(hipSetDevice(d.device));
   hipStream_t st = stream ? (hipStream_t)stream : s->own;
   // ---- what the pass ends in, and the buffers its attention and that tail need, made before any capture
-  const Tail tail = plan_tail(s, step, sc != nullptr);
+  const Tail tail = plan_tail(s, step, sc != nullptr, tk != nullptr);
   if (verify && !s->vf_acc) {  // first verify call: split partials of the attention, keys and ids of every position
     const int stride = attention_verify_split_stride(d.n_head, s->max_chunks);
     Carver c;
@@ -1718,6 +1829,10 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
       return fail(BS_ERR_OOM, "verify buffers allocation failed (" + std::to_string(c.total) + " B)");
     s->owned.push_back({c.base, c.total});
     s->vf_stride = stride;
+  }
+  if (tail.kind == TAIL_TOPK_LOGPROBS) {
+    int rc = topk_buffers(s);
+    if (rc != BS_OK) return rc;
   }
   if (tail.kind == TAIL_VERIFY_DRAW) {
     int rc = verify_draw_buffers(s, !want_logits);  // host-I/O logits go through the logits staging
@@ -1734,13 +1849,14 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   s->past_next_valid = false;  // until this forward is enqueued
   const bool graph = (S == 1 || verify) && !host_io && s->prof.cls == 0 && s->graphs_on && !sc;  // scoring is always eager
   hipGraphExec_t exec = nullptr;
-  const GraphKey key{B, S, slot, step->flags, tail.kind, in, out, logits, st};
+  GraphKey key{B, S, slot, step->flags, tail.kind, in, out, logits, st};
+  if (tk) { key.out = tk->ids; key.logits = tk->logits; key.k = tk->k; key.logprobs = tk->logprobs; key.lse = tk->lse; }
   if (graph && !(exec = find_graph(s, key))) {
     hipGraph_t gr = nullptr;
     BS_TRACE("hipStreamBeginCapture");
     HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
     BS_TRACE("enqueue_forward (capturing)");
-    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts);
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, nullptr, tk);
     BS_TRACE("hipStreamEndCapture");
     hipError_t ce = hipStreamEndCapture(st, &gr);
     if (rc != BS_OK) { if (gr) hipGraphDestroy(gr); return rc; }
@@ -1761,7 +1877,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     HIP_TRY(hipGraphLaunch(exec, st));
   } else {
     BS_TRACE("enqueue_forward (eager)");
-    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, sc);
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, sc, tk);
     if (rc != BS_OK) return rc;
   }
   BS_TRACE("hipGetLastError");
@@ -1814,4 +1930,27 @@ extern "C" int bs_forward_score(bs_stage* s, const bs_step* step, const void* in
   }
   const ScoreIO sc{targets, top_ids, scores};
   return forward_impl(s, step, in, nullptr, nullptr, &sc, stream);
+}
+
+// The top-k log-prob tail (beam_topk.hip): argument and state checks, then a forward whose tail is
+// TAIL_TOPK_LOGPROBS (forward_impl makes the buffers of the first call after its own checks, before any capture).
+extern "C" int bs_forward_topk(bs_stage* s, const bs_step* step, const void* in, int32_t k, int32_t* ids, float* logprobs,
+                               float* lse, float* logits, void* stream) {
+  if (!s || !step) return fail(BS_ERR_INVALID, "stage/step is NULL");
+  const bs_stage_desc& d = s->d;
+  if (k < 1 || k > kTopkMaxK) return fail(BS_ERR_INVALID, "k must be in [1, 16]");
+  if (!ids || !logprobs) return fail(BS_ERR_INVALID, "ids/logprobs is NULL");
+  if (step->flags & (BS_STEP_VERIFY | BS_STEP_VERIFY_DRAW | BS_STEP_LOGITS))
+    return fail(BS_ERR_INVALID, "BS_STEP_VERIFY, BS_STEP_VERIFY_DRAW and BS_STEP_LOGITS are not valid for a top-k pass "
+                                "(the logits pointer says whether logits are wanted)");
+  if (!(step->flags & BS_STEP_HOST_IO) && logits && ((uintptr_t)logits & 15))
+    return fail(BS_ERR_INVALID, "device logits must be 16-byte aligned");
+  if (s->n_labels) return fail(BS_ERR_STATE, "bs_forward_topk on a classifier stage");
+  if (!d.is_last || !s->wemb || s->hv0 != 0 || s->hv1 != d.vocab)
+    return fail(BS_ERR_STATE, "bs_forward_topk needs the last stage of a generation model (ln_f + the whole lm_head)");
+  if (s->top_k > 1) return fail(BS_ERR_STATE, "bs_forward_topk needs the greedy pick (bs_set_sampling top_k <= 1)");
+  if (topk_slices(d.vocab) > kTopkMaxSlices) return fail(BS_ERR_UNSUPPORTED, "vocab too large for the top-k tail");
+  HIP_TRY(hipSetDevice(d.device));
+  const TopkIO tk{k, ids, logprobs, lse, logits};
+  return forward_impl(s, step, in, nullptr, nullptr, nullptr, stream, &tk);
 }

@@ -50,6 +50,11 @@ prefilled once, into a template KV row behind the pool's rows; an admitted sampl
 (bs_fork_kv, a device copy of the P cached positions on every rank) and prefills only the rest of its prompt at
 past = P.  The schedule is unchanged.  --prefix-fork 0 is the A/B baseline: every sample prefills the prefix in its own
 row with a pass of the same shape, then the rest, so both settings return the same tokens.
+--num-beams W is beam search on one GPU (beam.py; no counterpart in the reference): the samples are decoded one after
+another in KV rows [0, W) of the whole model as one stage; every step is one top-k log-prob pass (bs_forward_topk, the
+2W best tokens of each hypothesis), the selection of transformers' generate(num_beams=W) on the host (--length-penalty,
+--eos-id) and one bs_copy_kv call that hands the rows of dead hypotheses to the children of living ones.  Rank 0
+returns each sample's best hypothesis, its score and the number of KV row pairs copied.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
 unseeded top-k, token ids in (no tokenizer).
@@ -100,6 +105,9 @@ class RunConfig:
     sample_speculate: int = 0     # sampled speculative decoding: tokens drafted per verify-draw pass (0 = off; needs sample)
     shared_prefix: int = 0        # the first shared_prefix tokens of every prompt are identical and are prefilled once
     prefix_fork: bool = True      # shared_prefix: fork the template row (else every sample prefills the prefix itself)
+    num_beams: int = 0            # beam search: hypotheses per sample (0 = off; one GPU only)
+    length_penalty: float = 1.0   # beam search: a finished hypothesis scores sum(log p) / length ** length_penalty
+    eos_id: int = -1              # beam search: the token that finishes a hypothesis (-1 = none)
 
     def __post_init__(self):
         if self.shared_prefix < 0:
@@ -108,6 +116,17 @@ class RunConfig:
             if (not self.prefill or self.score or self.max_length <= 0 or self.speculate or self.sample_speculate):
                 raise ValueError("shared_prefix is plain generation with admission prefills: it excludes "
                                  "prefill = False, score, max_length == 0, speculate and sample_speculate")
+        if self.num_beams:
+            if not 1 <= self.num_beams <= 8:
+                raise ValueError(f"num_beams must be in [1, 8] (got {self.num_beams}): a top-k pass returns 16 candidates")
+            if (self.sample or self.speculate or self.sample_speculate or self.score or self.shared_prefix
+                    or self.max_length <= 0):
+                raise ValueError("num_beams is beam search, a generation task of its own: it excludes sample, speculate, "
+                                 "sample_speculate, score, shared_prefix and max_length <= 0")
+            if self.eos_id < -1:
+                raise ValueError(f"eos_id must be a token id or -1 for none (got {self.eos_id})")
+            if not float("-inf") < self.length_penalty < float("inf"):
+                raise ValueError(f"length_penalty must be finite (got {self.length_penalty})")
         if self.kv not in ("bf16", "int8"):
             raise ValueError(f"kv must be 'bf16' or 'int8' (got {self.kv!r})")
         if self.speculate:
@@ -188,6 +207,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     if (cfg.speculate or cfg.sample_speculate) and world != 1:
         raise ValueError("speculative decoding runs on one stage (world == 1): acceptance is data-dependent, the "
                          "pipeline's schedule is not")
+    if cfg.num_beams and world != 1:
+        raise ValueError("beam search runs on one stage (world == 1): which rows are copied is data-dependent, the "
+                         "pipeline's schedule is not")
     if cfg.sample and executor_factory is not None:
         raise ValueError("sample is the HIP stage's per-row sampler: not available with an executor_factory")
     if cfg.num_sample < 1 or cfg.max_length < 0 or cfg.core_pool_size < 1:
@@ -224,6 +246,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
         return _classify_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.speculate or cfg.sample_speculate:
         return _spec_run(cfg, model, device, prompts, lens, say)
+    if cfg.num_beams:
+        return _beam_run(cfg, model, device, prompts, lens, say)
     # samples in flight = n_mb micro-batches x mb rows: one micro-batch per stage keeps every stage
     # busy; the rest of the pool rides as rows of a micro-batch (one GPU: one batched decode)
     n_mb = min(cfg.core_pool_size, world)
@@ -500,6 +524,41 @@ def _spec_run(cfg, model, device, prompts, lens, say):
         res.update(sample=True, sample_seed=cfg.sample_seed, sample_speculate=k, **sampling)
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
     say(STATES[3], {})
+    return res
+
+
+def _beam_run(cfg, model, device, prompts, lens, say):
+    """--num-beams W (world == 1): the whole model as one stage with W KV rows, the samples decoded one after another
+    by beam.BeamSearcher.  Returns the generation task's record (a sample's tokens: its best hypothesis, which an
+    eos may end before max_length) plus the hypotheses' scores and the KV row pairs copied."""
+    from .beam import BeamSearcher
+    from .stage import Stage
+    dev = device.index if device.type == "cuda" and device.index is not None else 0
+    W = cfg.num_beams
+    if cfg.eos_id >= model.vocab:
+        raise ValueError(f"eos_id ({cfg.eos_id}) outside the vocabulary ({model.vocab})")
+    stage = Stage(model.hidden, model.n_head, model.n_layer, model.vocab, 0, model.n_layer, dtype=cfg.dtype, device=dev,
+                  max_batch=W, max_ctx=max(lens) + cfg.max_length + 1, max_tokens=max(max(lens), W), seed=cfg.seed,
+                  int8_weights=model.int8_weights, mxfp4_weights=model.mxfp4_weights, kv_int8=cfg.kv == "int8")
+    searcher = BeamSearcher([stage], W, length_penalty=cfg.length_penalty, eos=cfg.eos_id)
+    say(STATES[0], {"rank_layers": [0, model.n_layer], "stages": 1, "num_beams": W})
+    say(STATES[1], {"num_sample": cfg.num_sample, "max_length": cfg.max_length})
+    out, scores = [], []
+    t_start = time.perf_counter()
+    for p in prompts:
+        seqs, sc, _ = searcher.generate(p, cfg.max_length)
+        out.append(seqs[0])
+        scores.append(sc[0])
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t_start
+    res = {"samples": out, "num_sample": cfg.num_sample, "max_length": cfg.max_length,
+           "core_pool_size": cfg.core_pool_size, "stages": 1, "prompt_lens": lens, "seconds": dt,
+           "tokens_per_s": sum(len(t) for t in out) / dt, "num_beams": W, "length_penalty": cfg.length_penalty,
+           "scores": scores, "kv_copies": searcher.kv_copies}
+    say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
+    say(STATES[3], {})
+    stage.close()
     return res
 
 

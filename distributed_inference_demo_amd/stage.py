@@ -104,7 +104,7 @@ EXPORTS = [
     "bs_build_id", "bs_hbm_probe", "bs_mfma_probe", "bs_init_stage_file", "bs_weights_file_probe",
     "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
     "bs_forward_score", "bs_set_row_sampler", "bs_sample_logits", "bs_read_row_draw",
-    "bs_read_verify_draw", "bs_fork_kv",
+    "bs_read_verify_draw", "bs_fork_kv", "bs_copy_kv", "bs_forward_topk",
 ]
 
 _LIB = None
@@ -135,6 +135,8 @@ def lib():
         L.bs_reset_kv.argtypes = [vp, i32]
         L.bs_read_kv.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bs_fork_kv.argtypes = [vp, i32, i32, i32, i32, vp]
+        L.bs_copy_kv.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, i32, vp]
+        L.bs_forward_topk.argtypes = [vp, ctypes.POINTER(Step), vp, i32, vp, vp, vp, vp, vp]
         L.bs_release.argtypes = [vp]
         L.bs_release.restype = None
         L.bs_last_error.restype = ctypes.c_char_p
@@ -347,6 +349,36 @@ class Stage:
         self._advance(st, pasts, batch, seq, slot)
         return top, scores
 
+    # ---- top-k log-prob pass (bs_forward_topk; last stage of a generation model)
+    def forward_topk(self, inp, ids, logprobs, batch, seq, k, slot=0, past_len=None, lse=None, logits=None,
+                     stream=None):
+        """The k <= 16 best tokens of each row's last position on device pointers (stream ordered): ids int32
+        [batch][k] (larger logit first, the lower index first on ties), logprobs fp32 [batch][k], and optionally lse
+        fp32 [batch] and logits fp32 [batch][vocab].  Appends seq positions to the KV rows like forward(); seq == 1
+        replays a captured graph."""
+        st, pasts = self._step(batch, seq, slot, past_len, 0)
+        _check(lib().bs_forward_topk(self._h, ctypes.byref(st), _ptr(inp), int(k), _ptr(ids), _ptr(logprobs),
+                                     _ptr(lse), _ptr(logits), stream))
+        self._advance(st, pasts, batch, seq, slot)
+        return ids, logprobs
+
+    def forward_topk_host(self, x, batch, seq, k, slot=0, past_len=None, want_logits=False):
+        """forward_topk() with numpy in and out: returns (ids int32 [batch][k], logprobs fp32 [batch][k], lse fp32
+        [batch]) and, with want_logits, the logits fp32 [batch][vocab] as a fourth item."""
+        if self.is_first:
+            x = np.ascontiguousarray(x, dtype=np.int32).reshape(batch, seq)
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32).reshape(batch, seq, self.hidden)
+        ids = np.empty((batch, k), np.int32)
+        lp = np.empty((batch, k), np.float32)
+        lse = np.empty(batch, np.float32)
+        logits = np.empty((batch, self.vocab), np.float32) if want_logits else None
+        st, pasts = self._step(batch, seq, slot, past_len, BS_STEP_HOST_IO)
+        _check(lib().bs_forward_topk(self._h, ctypes.byref(st), x.ctypes.data, int(k), ids.ctypes.data, lp.ctypes.data,
+                                     lse.ctypes.data, _ptr(logits), None))
+        self._advance(st, pasts, batch, seq, slot)
+        return (ids, lp, lse, logits) if want_logits else (ids, lp, lse)
+
     def set_sampling(self, top_k=1, temperature=1.0, seed=0):
         """Tail token pick (bs_set_sampling): greedy for top_k <= 1, else seeded top-k sampling in
         decoding.cpp:24-66's order (last stage only)."""
@@ -483,6 +515,19 @@ class Stage:
             npos = self.past[src]
         _check(lib().bs_fork_kv(self._h, int(src), int(dst), int(count), int(npos), stream))
         self.past[dst:dst + count] = [int(npos)] * count
+
+    def copy_kv(self, pairs, npos, stream=None):
+        """bs_copy_kv: cached positions [0, npos) of row src to row dst for every (src, dst) of `pairs` (at most 32),
+        every layer of the stage (fork launches, one per run of pairs with one source and consecutive destinations).
+        No destination may be a source or appear twice.  Stream ordered like forward(); the destination rows then
+        stand at npos."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        n = len(pairs)
+        src = (ctypes.c_int32 * max(n, 1))(*[a for a, _ in pairs])
+        dst = (ctypes.c_int32 * max(n, 1))(*[b for _, b in pairs])
+        _check(lib().bs_copy_kv(self._h, src, dst, n, int(npos), stream))
+        for _, b in pairs:
+            self.past[b] = int(npos)
 
     def read_kv(self, layer, slot, pos0, npos):
         """KV row `slot` of local layer `layer`, positions [pos0, pos0+npos): fp32 [2 (K, V)][n_head][npos][hd]."""

@@ -13,7 +13,9 @@
  *                         all of which end in inference::run_inference (inference.cpp:145-218)
  *   bs_reset_kv        <- (none: the reference has no KV cache; new sample == new slot)
  *   bs_fork_kv         <- (none: no KV cache, so no shared prompt prefix to reuse)
+ *   bs_copy_kv         <- (none: no KV cache, so no hypotheses' rows to reorder)
  *   bs_forward_score   <- (none: the reference has no scoring task)
+ *   bs_forward_topk    <- (none: the reference's tail returns one token, decoding.cpp:24-66, never ranked candidates)
  *   bs_last_error      <- (none: the reference throws C++ exceptions across JNI,
  *                         native-lib.cpp:986-988; here errors are status codes + this string)
  *   bs_forward on a BS_FLAG_CLASSIFIER stage
@@ -261,6 +263,30 @@ int bs_forward(bs_stage *stage, const bs_step *step, const void *in, void *out, 
 int bs_forward_score(bs_stage *stage, const bs_step *step, const void *in, const int32_t *targets,
                      int32_t *top_ids, float *scores, void *stream);
 
+/* Top-k log-prob pass (last stage of a generation model with the whole lm_head; bf16 and fp32, and BS_FLAG_INT8_WEIGHTS /
+ * BS_FLAG_MXFP4_WEIGHTS / BS_FLAG_INT8_KV stages: the layers are bs_forward's): the k best tokens of each row's last
+ * position with their log-probabilities -- the step of beam search and of any "logprobs / n-best" request (DESIGN.md
+ * section 5i).  `step` and `in` are bs_forward's (B rows x S new tokens, per-row past_lens); BS_STEP_HOST_IO covers in,
+ * ids, logprobs, lse and logits.  Like bs_forward it appends S positions to the KV rows and its last kernel advances
+ * the device copy of each row's position by S; S == 1 on device buffers is captured and replayed like a decode step.
+ * bs_read_head_screen reports the full head afterwards (*count = -1).
+ *  With l[0..V) the fp32 logits of row b's last position (the values BS_STEP_LOGITS returns; every one finite):
+ *  ids: int32 [B][k], ids[b][j] = the index of the j-th largest logit; equal logits rank by the lower index first,
+ *       -0.0 and +0.0 are equal.  1 <= k <= 16.
+ *  lse: fp32 [B], m + logf(sum_v expf(l_v - m)) with m = max l; may be NULL.
+ *  logprobs: fp32 [B][k], l[ids[b][j]] - lse[b] (an fp32 subtraction).
+ *  logits: fp32 [B][V] (a device buffer is 16-byte aligned); NULL = not wanted.
+ * Given the logits the results are bit-identical from run to run and between graph replay and eager launch, and do
+ * not depend on the row index, the batch or the grid: no floating-point atomics, the partial sums are folded in a
+ * fixed order in which a term passes through at most 26 fp32 additions (beam_topk.hip).
+ * BS_ERR_INVALID: k outside [1, 16], NULL ids or logprobs, BS_STEP_VERIFY / BS_STEP_VERIFY_DRAW / BS_STEP_LOGITS in
+ * step->flags, bs_forward's shape checks.  BS_ERR_STATE: a classifier stage, a stage without the whole lm_head, after
+ * bs_set_sampling chose top_k > 1, a row of the call that holds sampler state.  BS_ERR_UNSUPPORTED: vocab > 2^21.
+ * The first call allocates the per-slice partials, the host-I/O staging and, if absent, the [max_batch][vocab] logits
+ * buffer of bs_set_row_sampler, counted under workspace_bytes from then on. */
+int bs_forward_topk(bs_stage *stage, const bs_step *step, const void *in, int32_t k, int32_t *ids, float *logprobs,
+                    float *lse, float *logits, void *stream);
+
 /* ---- Vocabulary-parallel head (stages with a head slice, or the last stage) ----
  * Argmax keys: uint64 (order(logit) << 32) | (0xFFFFFFFF - vocab_index), where order() maps
  * fp32 monotonically to uint32; the max key is the greedy token (lowest index on ties). */
@@ -405,6 +431,19 @@ int bs_read_kv(const bs_stage *stage, int32_t layer, int32_t slot, int32_t pos0,
  *   BS_OK and no launch for npos == 0, count == 0 or a stage without layers.  BS_ERR_INVALID: a NULL stage, a negative
  *   slot, count or npos, a slot range outside max_batch, npos > max_ctx, src_slot inside [dst_slot, dst_slot + count). */
 int bs_fork_kv(bs_stage *stage, int32_t src_slot, int32_t dst_slot, int32_t count, int32_t npos, void *stream);
+/* KV row pair copy: for i < count, cached positions [0, npos) of KV row src_slots[i] to row
+ * dst_slots[i] (host arrays, read before the call returns: no host-to-device copy, no device buffer), all layers of
+ * the stage, K and V, every head -- the reordering step of beam search, where children take over the rows of dead
+ * hypotheses.  A source may appear several times.  The rest of the contract is bs_fork_kv's: stream-ordered, no
+ * synchronisation, no allocation, captured graphs stay; an exact copy for bf16, fp32 and int8 caches (codes and scales
+ * verbatim, the scales in a launch of their own); nothing else is written.  The copies are bs_fork_kv's launches, one
+ * per run of consecutive pairs that share a source and whose destinations are consecutive rows (a one-launch
+ * pair-list kernel measured slower than those launches and was dropped).
+ *   BS_OK and no launch for count == 0, npos == 0 or a stage without layers.  BS_ERR_INVALID: a NULL stage, NULL lists
+ *   with count > 0, count outside [0, 32], a slot outside [0, max_batch), npos outside [0, max_ctx], a destination that
+ *   appears twice, a destination that is also a source (so the launches have no ordering hazard among themselves). */
+int bs_copy_kv(bs_stage *stage, const int32_t *src_slots, const int32_t *dst_slots, int32_t count, int32_t npos,
+               void *stream);
 
 void bs_release(bs_stage *stage);
 
