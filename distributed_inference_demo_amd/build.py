@@ -17,7 +17,7 @@ LIB = os.path.join(PKG, "lib", "libbloomstage.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "head_score.hip", "attn_verify.hip", "row_sample.hip", "kv_fork.hip", "beam_topk.hip", "stage.hip", "codec.cpp", "safetensors.cpp"]
+SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "head_score.hip", "attn_verify.hip", "row_sample.hip", "logit_proc.hip", "kv_fork.hip", "beam_topk.hip", "stage.hip", "codec.cpp", "safetensors.cpp"]
 # per-source extra flags: the prefill attention keeps its MFMA accumulators in VGPRs (attn_prefill.hip header)
 EXTRA = {"attn_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 HEADERS = ["common.h", "kernels.h", "attn_merge.h", "safetensors.h", "stage_weights.h"]

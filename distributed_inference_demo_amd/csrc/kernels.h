@@ -268,6 +268,36 @@ void launch_row_sample(const RowSampleBufs& rb, const float* logits, int ld, int
 void launch_row_sample_verify(const RowSampleBufs& vb, const float* logits, int ld, int V, int slot, int B, int S,
                               const int* past_dev, int* tokens, int* past_adv, hipStream_t s);
 
+// ---- Per-row logit processors (include/bloomstage.h "Per-row logit processors"; logit_proc.hip) ----
+constexpr int kRowBiasMax = 64;  // BS_ROW_BIAS_MAX
+struct RowProcDev {  // one entry of the device table [max_batch]; bs_row_processor plus `active`
+  float penalty;
+  int ngram, min_new, eos, n_bias;
+  int active;  // 0: the launches return at once for this row
+  int bias_ids[kRowBiasMax];
+  float bias_values[kRowBiasMax];
+};
+// Everything is indexed by KV row.  cap = max_ctx + 1 tokens a row; words = ceil(V / 32).
+struct LogitProcBufs {
+  RowProcDev* table;   // [max_batch]
+  int* hist;           // [max_batch][cap] the ordered token history
+  int* distinct;       // [max_batch][cap] each token of the history once, in no particular order
+  uint32_t* seen;      // [max_batch][words] bit v: token v is in the history
+  int* counts;         // [max_batch][4] = {history length, distinct tokens, generated tokens, unused}
+  int cap, words, V;
+};
+// table[slot .. slot + n) = rows[0..n) (host, by kernel arguments) and the rows' histories emptied: the seen words of
+// the distinct tokens back to zero (O(tokens noted)), the counts to zero.  Stream ordered.
+void launch_logit_proc_set(const LogitProcBufs& lp, int slot, const RowProcDev* rows, int n, hipStream_t s);
+// Append n tokens to row `slot`'s history, in order; ids outside [0, V) and tokens beyond cap are dropped.  ids_host:
+// read now and passed by kernel arguments; else ids_dev is read on the stream.  generated: also count them as generated.
+void launch_logit_proc_note(const LogitProcBufs& lp, int slot, const int* ids_host, const int* ids_dev, int n,
+                            int generated, hipStream_t s);
+// The tail's note: row slot + b with state appends tokens[b] and counts it as generated; rows without state return.
+void launch_logit_proc_note_picks(const LogitProcBufs& lp, int slot, int B, const int* tokens, hipStream_t s);
+// The rule in place on logits [B][ld] (V columns each) for rows [slot, slot + B); rows without state return at once.
+void launch_logit_proc_apply(const LogitProcBufs& lp, float* logits, int ld, int slot, int B, hipStream_t s);
+
 // ---- Weight-only int8 (bf16 stages with BS_FLAG_INT8_WEIGHTS; kernels.hip "Weight-only int8") ----
 // Q[n][k] = rne(W[n][k] / scale[n]), scale[n] = max_k |W[n][k]| / 127 (1 for a zero row); W bf16 [N][K].
 void launch_quantize_rows(const void* W_bf16, int8_t* Q, float* scale, int N, int K, hipStream_t s);

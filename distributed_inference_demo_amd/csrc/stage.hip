@@ -81,6 +81,8 @@ enum TailKind {
   TAIL_GREEDY,         // full head, argmax
   TAIL_TOPK,           // full head, bs_set_sampling's seeded top-k
   TAIL_ROWS,           // full head, per-row sampler (a row of the call holds sampler state)
+  TAIL_ROWS_PROC,      // full head with its logits written, the per-row logit processors on them, the per-row sampler as
+                       // the pick, the picks noted in the rows' histories (a row of the call holds processor state)
   TAIL_TOPK_LOGPROBS,  // bs_forward_topk: full head with its logits written, the k best ids and log-probs of each row
 };
 struct Tail {
@@ -91,8 +93,8 @@ struct Tail {
 
 struct GraphKey {
   int B, seq, slot, flags;
-  TailKind tail;  // row-sampler state changes the tail of otherwise equal calls (the setters that change it for
-                  // every call drop the graphs instead)
+  TailKind tail;  // row-sampler and row-processor state change the tail of otherwise equal calls: the kind is the
+                  // key's bit for the route (the setters that change it for every call drop the graphs instead)
   const void* in;
   void* out;
   float* logits;
@@ -265,6 +267,13 @@ struct bs_stage {
   RowSampleBufs rs{};
   std::vector<RowSamplerDev> rs_host;  // [max_batch]
   int rs_active = 0;                   // rows that hold state
+  // per-row logit processors (logit_proc.hip): the device table and the rows' token state, one allocation made by the
+  // first bs_set_row_processor / bs_process_logits (lp.table null: never used); lp_host mirrors what routing and the
+  // argument checks need: does the row hold state, and how long its history is (an upper bound of the device's)
+  LogitProcBufs lp{};
+  struct RowProcHost { int active = 0, len = 0; };
+  std::vector<RowProcHost> lp_host;  // [max_batch]
+  int lp_active = 0;                 // rows that hold state
   // BS_STEP_VERIFY_DRAW: the sampler scratch of kVerifyMaxTokens positions (vd, made by the first verify-draw pass
   // that runs the sampler) and the [max(max_batch, kVerifyMaxTokens)][V] logits its tail reads when the caller
   // gives no device logits (vd_logits, made by the first such pass); vd_last_*: the shape of the last such pass
@@ -1194,6 +1203,14 @@ static bool rows_sampled(const bs_stage* s, int slot, int B) {
   return false;
 }
 
+// Does a row of [slot, slot + B) hold processor state (bs_set_row_processor)?  Then the tail applies it before the pick.
+static bool rows_processed(const bs_stage* s, int slot, int B) {
+  if (!s->lp_active) return false;
+  for (int b = 0; b < B; b++)
+    if (s->lp_host[slot + b].active) return true;
+  return false;
+}
+
 // Which tail this pass ends in (scoring: a bs_forward_score pass).  forward_impl has checked the step against the stage.
 static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring, bool topk = false) {
   const int B = step->batch, M = B * step->seq, V = s->d.vocab;
@@ -1204,6 +1221,7 @@ static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring, bool
   const bool rows = rows_sampled(s, step->slot, B);  // excludes top_k > 1 (bs_set_row_sampler / bs_set_sampling)
   if (step->flags & BS_STEP_VERIFY)
     return Tail{rows && (step->flags & BS_STEP_VERIFY_DRAW) ? TAIL_VERIFY_DRAW : TAIL_VERIFY_ARGMAX, M, V};
+  if (rows_processed(s, step->slot, B)) return Tail{TAIL_ROWS_PROC, B, V};  // forward_impl has excluded verify passes
   if (rows) return Tail{TAIL_ROWS, B, V};
   if (s->top_k > 1) return Tail{TAIL_TOPK, B, V};
   if (s->hs_on && s->hs.Q && !(step->flags & BS_STEP_LOGITS) && head_screen_supported(B, s->d.hidden))
@@ -1437,9 +1455,10 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
     case TAIL_SCREENED:
     case TAIL_GREEDY:
     case TAIL_TOPK:
-    case TAIL_ROWS: {
+    case TAIL_ROWS:
+    case TAIL_ROWS_PROC: {
       // ln_f on each row's last position, tied lm_head, token pick
-      const bool reads_logits = tail.kind == TAIL_TOPK || tail.kind == TAIL_ROWS;
+      const bool reads_logits = tail.kind == TAIL_TOPK || tail.kind == TAIL_ROWS || tail.kind == TAIL_ROWS_PROC;
       Epi e{};
       e.kind = EPI_ARGMAX; e.keys = s->keys; e.ldo = V;
       e.key_hi_index = tail.kind == TAIL_TOPK ? 1 : 0;  // sampling ranks equal logits by the higher index (decoding.cpp:44-45)
@@ -1457,12 +1476,16 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
                          s->past_dev, S, st);
       } else {
         linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
-        if (tail.kind == TAIL_ROWS)  // rows of the call without state get the first index of their largest logit
+        if (tail.kind == TAIL_ROWS_PROC)  // in place: BS_STEP_LOGITS returns what the pick saw
+          launch_logit_proc_apply(s->lp, e.logits, V, slot, B, st);
+        if (tail.kind == TAIL_ROWS || tail.kind == TAIL_ROWS_PROC)  // rows of the call without state get the first index of their largest logit
           launch_row_sample(s->rs, e.logits, V, V, slot, B, nullptr, past_dev, S, tok_out, s->past_dev, st);
-        else if (tail.kind == TAIL_TOPK)
+        if (tail.kind == TAIL_ROWS_PROC)  // each row with processor state appends its pick to its history
+          launch_logit_proc_note_picks(s->lp, slot, B, tok_out, st);
+        if (tail.kind == TAIL_TOPK)
           launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
                              past_dev, S, tok_out, st, s->past_dev);
-        else
+        if (tail.kind == TAIL_GREEDY)
           launch_argmax_finalize(s->keys, B, V / 16, nullptr, nullptr, tok_out, st, s->past_dev, S);
       }
       return tail_copy_out(tail, step, s->tok, out, staged, logits, st);
@@ -1556,6 +1579,7 @@ extern "C" int bs_set_sampling(bs_stage* s, int32_t top_k, float temperature, ui
     return fail(BS_ERR_UNSUPPORTED, "sampling needs the last stage of a generation model (whole lm_head)");
   if (top_k > 1 && !(temperature > 0.f)) return fail(BS_ERR_INVALID, "temperature must be positive");
   if (top_k > 1 && s->rs_active) return fail(BS_ERR_STATE, "rows hold per-row sampler state (bs_set_row_sampler)");
+  if (top_k > 1 && s->lp_active) return fail(BS_ERR_STATE, "rows hold logit processor state (bs_set_row_processor)");
   HIP_TRY(hipSetDevice(s->d.device));
   if (top_k > 1 && !s->sample_logits) {
     HIP_TRY(hipStreamSynchronize(s->own));
@@ -1675,6 +1699,141 @@ extern "C" int bs_read_row_draw(bs_stage* s, int32_t slot, bs_row_draw* out) {
   HIP_TRY(hipSetDevice(s->d.device));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, s->rs.draw + slot, sizeof(*out), hipMemcpyDeviceToHost));
+  return BS_OK;
+}
+
+// ---- per-row logit processors (logit_proc.hip)
+static_assert(sizeof(bs_row_processor) + 4 == sizeof(RowProcDev) && BS_ROW_BIAS_MAX == kRowBiasMax, "bs_row_processor layout");
+
+// The table and the rows' token state (zeroed), and the row sampler's buffers: its launches are the pick of a processed
+// step, and its [max_batch][V] logits buffer is what the head writes when the caller gives none.
+static int logit_proc_buffers(bs_stage* s) {
+  if (s->lp.table) return BS_OK;
+  int rc = row_sampler_buffers(s);
+  if (rc != BS_OK) return rc;
+  const size_t mb = s->d.max_batch, cap = (size_t)s->d.max_ctx + 1, words = ((size_t)s->d.vocab + 31) / 32;
+  LogitProcBufs lp{};
+  Carver c;
+  c.piece(&lp.table, mb * sizeof(RowProcDev));
+  c.piece(&lp.hist, mb * cap * 4);
+  c.piece(&lp.distinct, mb * cap * 4);
+  c.piece(&lp.seen, mb * words * 4);
+  c.piece(&lp.counts, mb * 4 * 4);
+  const int ar = c.alloc(s->own);
+  if (ar == Carver::NO_MEMORY) return fail(BS_ERR_OOM, "logit processor buffers allocation failed (" + std::to_string(c.total) + " B)");
+  if (ar == Carver::NOT_ZEROED) return fail(BS_ERR_DEVICE, "logit processor buffers memset");
+  lp.cap = (int)cap; lp.words = (int)words; lp.V = s->d.vocab;
+  s->owned.push_back({c.base, c.total});
+  s->lp = lp;
+  s->lp_host.assign(mb, bs_stage::RowProcHost{});
+  return BS_OK;
+}
+
+extern "C" int bs_set_row_processor(bs_stage* s, int32_t slot, int32_t count, const bs_row_processor* params, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  int rc = row_sampler_stage_check(s);
+  if (rc) return fail(BS_ERR_UNSUPPORTED, "logit processors need the last stage of a generation model (whole lm_head)");
+  if (count <= 0 || slot < 0 || slot > s->d.max_batch - count) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (params && s->top_k > 1) return fail(BS_ERR_STATE, "bs_set_sampling holds top_k > 1");
+  const int V = s->d.vocab;
+  std::vector<RowProcDev> rows(count, RowProcDev{});
+  for (int i = 0; params && i < count; i++) {
+    const bs_row_processor& p = params[i];
+    if (!std::isfinite(p.repetition_penalty) || !(p.repetition_penalty > 0.f))
+      return fail(BS_ERR_INVALID, "repetition_penalty must be positive and finite");
+    if (p.no_repeat_ngram < 0 || p.no_repeat_ngram > 32) return fail(BS_ERR_INVALID, "no_repeat_ngram must be in [0, 32]");
+    if (p.min_new_tokens < 0) return fail(BS_ERR_INVALID, "min_new_tokens must be >= 0");
+    if (p.eos_id >= V) return fail(BS_ERR_INVALID, "eos_id must be below vocab (negative: none)");
+    if (p.n_bias < 0 || p.n_bias > BS_ROW_BIAS_MAX) return fail(BS_ERR_INVALID, "n_bias must be in [0, 64]");
+    RowProcDev& r = rows[i];
+    r.penalty = p.repetition_penalty; r.ngram = p.no_repeat_ngram; r.min_new = p.min_new_tokens;
+    r.eos = p.eos_id < 0 ? -1 : p.eos_id; r.n_bias = p.n_bias; r.active = 1;
+    for (int j = 0; j < p.n_bias; j++) {
+      if (p.bias_ids[j] < 0 || p.bias_ids[j] >= V) return fail(BS_ERR_INVALID, "bias id outside [0, vocab)");
+      if (std::isnan(p.bias_values[j]) || p.bias_values[j] == INFINITY)
+        return fail(BS_ERR_INVALID, "bias value must be finite or -inf (a ban)");
+      r.bias_ids[j] = p.bias_ids[j];
+      r.bias_values[j] = p.bias_values[j];
+    }
+  }
+  if (!params && !s->lp.table) return BS_OK;  // nothing was ever set
+  HIP_TRY(hipSetDevice(s->d.device));
+  if ((rc = logit_proc_buffers(s)) != BS_OK) return rc;
+  launch_logit_proc_set(s->lp, slot, rows.data(), count, stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("logit processor table: ") + hipGetErrorString(err));
+  for (int i = 0; i < count; i++) {
+    s->lp_active += rows[i].active - s->lp_host[slot + i].active;
+    s->lp_host[slot + i].active = rows[i].active;
+    s->lp_host[slot + i].len = 0;
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_note_tokens(bs_stage* s, int32_t slot, const int32_t* ids, int32_t n, int32_t flags, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot out of range");
+  if (flags & ~(BS_STEP_HOST_IO | BS_NOTE_GENERATED)) return fail(BS_ERR_INVALID, "only BS_STEP_HOST_IO and BS_NOTE_GENERATED are valid here");
+  if (n < 0 || (n > 0 && !ids)) return fail(BS_ERR_INVALID, "bad ids / n");
+  if (!s->lp.table || !s->lp_host[slot].active) return fail(BS_ERR_STATE, "the row holds no logit processor state");
+  if (s->lp_host[slot].len + n > s->lp.cap) return fail(BS_ERR_INVALID, "the row's token history would exceed max_ctx + 1");
+  const bool host = (flags & BS_STEP_HOST_IO) != 0;
+  if (host)
+    for (int i = 0; i < n; i++)
+      if (ids[i] < 0 || ids[i] >= s->d.vocab) return fail(BS_ERR_INVALID, "token id out of range");
+  if (n == 0) return BS_OK;
+  HIP_TRY(hipSetDevice(s->d.device));
+  launch_logit_proc_note(s->lp, slot, host ? ids : nullptr, host ? nullptr : ids, n, (flags & BS_NOTE_GENERATED) ? 1 : 0,
+                         stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("note tokens: ") + hipGetErrorString(err));
+  s->lp_host[slot].len += n;
+  return BS_OK;
+}
+
+extern "C" int bs_process_logits(bs_stage* s, int32_t slot, int32_t batch, float* logits, int32_t ld, int32_t flags,
+                                 void* stream) {
+  if (!s || !logits) return fail(BS_ERR_INVALID, "stage/logits is NULL");
+  if (row_sampler_stage_check(s)) return BS_ERR_UNSUPPORTED;
+  const int V = s->d.vocab;
+  if (batch <= 0 || slot < 0 || slot > s->d.max_batch - batch) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (ld < V) return fail(BS_ERR_INVALID, "ld must be >= vocab");
+  if (flags & ~BS_STEP_HOST_IO) return fail(BS_ERR_INVALID, "only BS_STEP_HOST_IO is valid here");
+  HIP_TRY(hipSetDevice(s->d.device));
+  int rc = logit_proc_buffers(s);
+  if (rc != BS_OK) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  const bool host_io = (flags & BS_STEP_HOST_IO) != 0;
+  float* dl = logits;
+  const size_t n = (size_t)(batch - 1) * ld + V;  // the last row may end at its V-th column
+  if (host_io) {
+    if ((rc = logits_staging(s, (size_t)batch * ld * 4, st, &dl)) != BS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(dl, logits, n * 4, hipMemcpyHostToDevice, st));
+  }
+  launch_logit_proc_apply(s->lp, dl, ld, slot, batch, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("logit processors: ") + hipGetErrorString(err));
+  if (host_io) {
+    HIP_TRY(hipMemcpyAsync(logits, dl, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_read_row_tokens(bs_stage* s, int32_t slot, int32_t* tokens, int32_t* n_tokens, int32_t* n_generated,
+                                  int32_t* n_distinct) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot out of range");
+  if (!s->lp.table) return fail(BS_ERR_STATE, "the stage never used the logit processors");
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());
+  int cnt[4];
+  HIP_TRY(hipMemcpy(cnt, s->lp.counts + (size_t)slot * 4, sizeof(cnt), hipMemcpyDeviceToHost));
+  const int len = std::min(std::max(cnt[0], 0), s->lp.cap);
+  if (tokens && len) HIP_TRY(hipMemcpy(tokens, s->lp.hist + (size_t)slot * s->lp.cap, (size_t)len * 4, hipMemcpyDeviceToHost));
+  if (n_tokens) *n_tokens = len;
+  if (n_generated) *n_generated = cnt[2];
+  if (n_distinct) *n_distinct = cnt[1];
   return BS_OK;
 }
 
@@ -1805,6 +1964,8 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   }
   if (!in || (!out && !sc && !tk)) return fail(BS_ERR_INVALID, "in/out is NULL");
   if (tk && rows_sampled(s, slot, B)) return fail(BS_ERR_STATE, "bs_forward_topk on a row that holds sampler state");
+  if (!sc && (tk || verify) && rows_processed(s, slot, B))
+    return fail(BS_ERR_STATE, "bs_forward_topk / BS_STEP_VERIFY on a row that holds logit processor state");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   if (want_logits && (!d.is_last || !logits)) return fail(BS_ERR_INVALID, "logits requested on a non-last stage or NULL");
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
@@ -1885,6 +2046,9 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
   s->hs_last_rows = tail.kind == TAIL_SCREENED ? B : 0;
   if (tail.kind == TAIL_VERIFY_DRAW) { s->vd_last_slot = slot; s->vd_last_B = B; s->vd_last_S = S; }
+  if (tail.kind == TAIL_ROWS_PROC)  // the note launch appended one pick to every row with state
+    for (int b = 0; b < B; b++)
+      if (s->lp_host[slot + b].active) s->lp_host[slot + b].len = std::min(s->lp_host[slot + b].len + 1, s->lp.cap);
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)
     s->past_next.assign(pasts.begin(), pasts.end());
     for (int& p : s->past_next) p += S;

@@ -100,6 +100,22 @@ class StageExecutor:
             return
         self._run(call, ())
 
+    def set_row_processor(self, slot, prompt=None, **state):
+        """Stage.set_row_processor of KV row `slot` followed by note_tokens of `prompt` (state given), or
+        clear_row_processor (no state), ordered like forward."""
+        def call(h):
+            if state:
+                self.stage.set_row_processor(slot, stream=h, **state)
+                if prompt is not None and len(prompt):
+                    self.stage.note_tokens(slot, prompt, stream=h)
+            else:
+                self.stage.clear_row_processor(slot, 1, stream=h)
+        sh = self._sh if self._sh is not None else torch.cuda.current_stream().cuda_stream
+        if sh:
+            call(sh)
+            return
+        self._run(call, ())
+
     def fork_kv(self, src, dst, npos, count=1):
         """Stage.fork_kv: positions [0, npos) of KV row `src` copied to rows [dst, dst + count), ordered like
         forward."""
@@ -385,6 +401,16 @@ class Pipeline:
             if self.head_split:
                 raise ValueError("per-row sampling needs the whole lm_head on the last stage: build_rank(sample=True)")
             self.ex.set_row_sampler(mb * self.mb + row, **state)
+
+    def set_row_processor(self, mb, row, prompt=None, **state):
+        """Per-row logit processors (bs_set_row_processor, bs_note_tokens): give row `row` of micro-batch `mb` the
+        processor state (Stage.row_processor's keywords) with `prompt` (a list of token ids: the sample's whole
+        prompt) as its token history, or clear it when no state is given.  Acts on the last rank, which holds the
+        whole lm_head (build_rank(..., sample=True)), ordered with its forwards; a no-op elsewhere."""
+        if self.is_last:
+            if self.head_split:
+                raise ValueError("logit processors need the whole lm_head on the last stage: build_rank(sample=True)")
+            self.ex.set_row_processor(mb * self.mb + row, prompt=prompt, **state)
 
     def finish(self, record=None):
         """Rank 0 collects the tokens of the last round; everyone drains its sends.  Later steps

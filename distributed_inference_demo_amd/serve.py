@@ -55,6 +55,14 @@ another in KV rows [0, W) of the whole model as one stage; every step is one top
 2W best tokens of each hypothesis), the selection of transformers' generate(num_beams=W) on the host (--length-penalty,
 --eos-id) and one bs_copy_kv call that hands the rows of dead hypotheses to the children of living ones.  Rank 0
 returns each sample's best hypothesis, its score and the number of KV row pairs copied.
+--repetition-penalty R, --no-repeat-ngram-size N, --min-new-tokens M (with --eos-id), --bad-token ID and --token-bias
+ID:VALUE (both repeatable) are the per-row logit processors (bs_set_row_processor; transformers'
+repetition_penalty, no_repeat_ngram_size, min_new_tokens, length-1 bad_words_ids and sequence_bias): at admission the
+last rank gives the sample's row the state and notes the sample's whole prompt (a shared prefix included) as the row's
+token history, just before the prefill pass that yields the first generated token; from then on the device notes its
+own picks.  The last rank holds the prompts (they are broadcast once at start when world > 1) and the whole lm_head.
+They combine with --sample (the processed logits are what the sampler draws from), --shared-prefix, --kv int8 and
+int8 / MXFP4 weights.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
 unseeded top-k, token ids in (no tokenizer).
@@ -107,11 +115,46 @@ class RunConfig:
     prefix_fork: bool = True      # shared_prefix: fork the template row (else every sample prefills the prefix itself)
     num_beams: int = 0            # beam search: hypotheses per sample (0 = off; one GPU only)
     length_penalty: float = 1.0   # beam search: a finished hypothesis scores sum(log p) / length ** length_penalty
-    eos_id: int = -1              # beam search: the token that finishes a hypothesis (-1 = none)
+    eos_id: int = -1              # beam search: the token that finishes a hypothesis; min_new_tokens: the banned one (-1 = none)
+    repetition_penalty: float = 1.0   # logit processors: seen tokens' logits divided (> 0) / multiplied (< 0); 1 = off
+    no_repeat_ngram_size: int = 0     # logit processors: no n-gram of this size twice (0 = off, else 1..32)
+    min_new_tokens: int = 0           # logit processors: eos_id is banned for a sample's first min_new_tokens tokens
+    bad_token: tuple = ()             # logit processors: banned token ids (at most 64 with token_bias)
+    token_bias: tuple = ()            # logit processors: (id, value) pairs or "ID:VALUE" strings, value added to the logit
+
+    @property
+    def processors(self):
+        """Stage.row_processor's keywords when any logit processor is on, else None."""
+        if (self.repetition_penalty == 1.0 and not self.no_repeat_ngram_size and not self.min_new_tokens
+                and not self.bad_token and not self.token_bias):
+            return None
+        return {"repetition_penalty": self.repetition_penalty, "no_repeat_ngram": self.no_repeat_ngram_size,
+                "min_new_tokens": self.min_new_tokens, "eos_id": self.eos_id if self.min_new_tokens else -1,
+                "bias": list(self.token_bias), "bad_tokens": list(self.bad_token)}
 
     def __post_init__(self):
         if self.shared_prefix < 0:
             raise ValueError(f"shared_prefix must be >= 0 (got {self.shared_prefix})")
+        self.bad_token = tuple(int(t) for t in self.bad_token)
+        self.token_bias = tuple((int(str(e).split(":")[0]), float(str(e).split(":")[1])) if isinstance(e, str)
+                                else (int(e[0]), float(e[1])) for e in self.token_bias)
+        if self.processors:
+            if (self.speculate or self.sample_speculate or self.num_beams or self.score or self.max_length <= 0
+                    or not self.prefill):
+                raise ValueError("the logit processors (repetition_penalty, no_repeat_ngram_size, min_new_tokens, "
+                                 "bad_token, token_bias) are plain generation with admission prefills: they exclude "
+                                 "speculate, sample_speculate, num_beams, score, max_length == 0 and prefill = False")
+            if not 0.0 < self.repetition_penalty < float("inf"):
+                raise ValueError(f"repetition_penalty must be positive and finite (got {self.repetition_penalty})")
+            if not 0 <= self.no_repeat_ngram_size <= 32:
+                raise ValueError(f"no_repeat_ngram_size must be in [0, 32] (got {self.no_repeat_ngram_size})")
+            if self.min_new_tokens < 0 or (self.min_new_tokens and self.eos_id < 0):
+                raise ValueError("min_new_tokens must be >= 0 and needs eos_id, the token it bans")
+            if len(self.bad_token) + len(self.token_bias) > 64:
+                raise ValueError("at most 64 bad_token and token_bias entries together")
+            if any(v != v or v == float("inf") for _, v in self.token_bias):
+                raise ValueError("a token_bias value must be finite (or -inf: a ban)")
+            self.head_split = False  # the whole lm_head on the last stage, as for sample
         if self.shared_prefix:
             if (not self.prefill or self.score or self.max_length <= 0 or self.speculate or self.sample_speculate):
                 raise ValueError("shared_prefix is plain generation with admission prefills: it excludes "
@@ -212,6 +255,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
                          "pipeline's schedule is not")
     if cfg.sample and executor_factory is not None:
         raise ValueError("sample is the HIP stage's per-row sampler: not available with an executor_factory")
+    proc = cfg.processors
+    if proc and executor_factory is not None:
+        raise ValueError("the logit processors are the HIP stage's: not available with an executor_factory")
     if cfg.num_sample < 1 or cfg.max_length < 0 or cfg.core_pool_size < 1:
         raise ValueError("num_sample and core_pool_size must be >= 1, max_length >= 0 (0: classification)")
     model = config.get(cfg.model) if isinstance(cfg.model, str) else cfg.model
@@ -240,6 +286,21 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
                              "continuation pass needs a token")
         if differ:
             raise ValueError(f"shared_prefix = {P}: the prompts' first {P} tokens differ")
+    if proc:
+        if any(not 0 <= t < model.vocab for t in list(cfg.bad_token) + [t for t, _ in cfg.token_bias]):
+            raise ValueError(f"a bad_token / token_bias id lies outside the vocabulary ({model.vocab})")
+        if cfg.min_new_tokens and cfg.eos_id >= model.vocab:
+            raise ValueError(f"eos_id ({cfg.eos_id}) outside the vocabulary ({model.vocab})")
+        if world > 1:  # the last rank notes every sample's prompt: the prompts travel once, behind their lengths
+            flat = torch.tensor([t for p in prompts for t in p] if rank == 0 else [0] * sum(lens), dtype=torch.int64)
+            if dist.get_backend() == "nccl":
+                flat = flat.to(device)
+            dist.broadcast(flat, src=0)
+            if rank == world - 1 and rank != 0:
+                flat, prompts, at = flat.tolist(), [], 0
+                for n in lens:
+                    prompts.append(flat[at:at + n])
+                    at += n
     if cfg.score:
         return _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.max_length == 0:
@@ -282,7 +343,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + cfg.max_length + 1, max_seq=max_seq, seed=cfg.seed,
                                 head_split=cfg.head_split, executor_factory=executor_factory,
-                                kv_int8=cfg.kv == "int8", sample=cfg.sample, extra_rows=int(fork))
+                                kv_int8=cfg.kv == "int8", sample=cfg.sample or bool(proc), extra_rows=int(fork))
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "rounds": T, "prefill": pf,
                     **({"shared_prefix": P, "prefix_fork": fork} if P else {})})
@@ -321,6 +382,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
             elif P:  # the A/B baseline: a pass of the template's shape computes the prefix in the row itself
                 pipe.prefill_row(r // mb, r % mb, pre[i], P)
                 prefill_tokens += P
+            if proc and rank == world - 1:  # the row's processor state and its history, the whole prompt (a forked or
+                # prefilled prefix included), ordered before the pass whose tail yields the first generated token
+                pipe.set_row_processor(r // mb, r % mb, prompt=prompts[i], **proc)
             if P:  # the rest of the prompt behind the prefix; its tail yields the first generated token
                 tok = pipe.prefill_row(r // mb, r % mb, rest[i], lens[i] - P, past=P)
             else:
@@ -357,6 +421,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
            "prefill": pf, "seconds": dt, "tokens_per_s": cfg.num_sample * cfg.max_length / dt}
     if sampling:
         res.update(sample=True, sample_seed=cfg.sample_seed, **sampling)
+    if proc:
+        res.update(processors={k: v for k, v in proc.items() if k not in ("bias", "bad_tokens")},
+                   token_bias=[list(e) for e in cfg.token_bias], bad_token=list(cfg.bad_token))
     if P:  # prefill_tokens: the tokens pushed through prefill passes, the template's included
         res.update(shared_prefix=P, prefix_fork=fork, prefill_tokens=prefill_tokens)
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
@@ -566,7 +633,9 @@ def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     for f in dataclasses.fields(RunConfig):
         flag = "--" + f.name.replace("_", "-")
-        if f.type is bool or f.type == "bool":
+        if f.type is tuple or f.type == "tuple":  # repeatable: --bad-token ID, --token-bias ID:VALUE
+            p.add_argument(flag, action="append", default=[], type=int if f.name == "bad_token" else str)
+        elif f.type is bool or f.type == "bool":
             p.add_argument(flag, type=int, nargs="?", const=1, default=int(f.default))  # `--score` == `--score 1`
         else:
             p.add_argument(flag, type=type(f.default), default=f.default)

@@ -41,6 +41,8 @@ BS_STEP_HOST_IO = 1
 BS_STEP_LOGITS = 2
 BS_STEP_VERIFY = 4        # bs_step.flags: short verify pass (2 <= seq <= 8), greedy ids at every position
 BS_STEP_VERIFY_DRAW = 8   # bs_step.flags, with BS_STEP_VERIFY: the row sampler's draw at every position
+BS_NOTE_GENERATED = 16    # bs_note_tokens flags: the noted tokens also count as generated
+BS_ROW_BIAS_MAX = 64
 BS_FLAG_INT8_WEIGHTS = 1  # bs_stage_desc.flags: weight-only int8 block matrices
 BS_FLAG_CLASSIFIER = 2    # bs_stage_desc.flags: sequence-classification tail (score head, class ids out)
 BS_FLAG_INT8_KV = 4       # bs_stage_desc.flags: int8 KV cache, one fp32 scale per (position, head) vector
@@ -84,6 +86,13 @@ class RowSampler(ctypes.Structure):
                 ("seed", ctypes.c_uint64)]
 
 
+class RowProcessor(ctypes.Structure):
+    """bs_row_processor: the logit processor parameters of one KV row."""
+    _fields_ = [("repetition_penalty", ctypes.c_float), ("no_repeat_ngram", ctypes.c_int32),
+                ("min_new_tokens", ctypes.c_int32), ("eos_id", ctypes.c_int32), ("n_bias", ctypes.c_int32),
+                ("bias_ids", ctypes.c_int32 * BS_ROW_BIAS_MAX), ("bias_values", ctypes.c_float * BS_ROW_BIAS_MAX)]
+
+
 class RowDraw(ctypes.Structure):
     """bs_row_draw: read-out of a row's last draw."""
     _fields_ = [("threshold", ctypes.c_float), ("n_nucleus", ctypes.c_int32), ("n_candidates", ctypes.c_int32),
@@ -105,6 +114,7 @@ EXPORTS = [
     "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
     "bs_forward_score", "bs_set_row_sampler", "bs_sample_logits", "bs_read_row_draw",
     "bs_read_verify_draw", "bs_fork_kv", "bs_copy_kv", "bs_forward_topk",
+    "bs_set_row_processor", "bs_note_tokens", "bs_process_logits", "bs_read_row_tokens",
 ]
 
 _LIB = None
@@ -165,6 +175,10 @@ def lib():
         L.bs_sample_logits.argtypes = [vp, i32, i32, ctypes.POINTER(i32), vp, i32, vp, i32, vp]
         L.bs_read_row_draw.argtypes = [vp, i32, ctypes.POINTER(RowDraw)]
         L.bs_read_verify_draw.argtypes = [vp, i32, i32, ctypes.POINTER(RowDraw)]
+        L.bs_set_row_processor.argtypes = [vp, i32, i32, ctypes.POINTER(RowProcessor), vp]
+        L.bs_note_tokens.argtypes = [vp, i32, vp, i32, i32, vp]
+        L.bs_process_logits.argtypes = [vp, i32, i32, vp, i32, i32, vp]
+        L.bs_read_row_tokens.argtypes = [vp, i32, vp] + [ctypes.POINTER(i32)] * 3
         L.bs_set_graphs.argtypes = [vp, i32]
         L.bs_set_head_screen.argtypes = [vp, i32]
         L.bs_read_head_screen.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(i32)]
@@ -435,6 +449,69 @@ class Stage:
         d = RowDraw()
         _check(lib().bs_read_verify_draw(self._h, int(slot), int(t), ctypes.byref(d)))
         return {name: getattr(d, name) for name, _ in RowDraw._fields_}
+
+    # ---- per-row logit processors (bs_set_row_processor; last stage of a generation model)
+    @staticmethod
+    def row_processor(repetition_penalty=1.0, no_repeat_ngram=0, min_new_tokens=0, eos_id=-1, bias=(), bad_tokens=()):
+        """A RowProcessor from keyword values: bias = (token, value) pairs or a dict, bad_tokens = banned ids (entries
+        of -inf)."""
+        ent = [(int(t), float(v)) for t, v in (bias.items() if isinstance(bias, dict) else bias)]
+        ent += [(int(t), float("-inf")) for t in bad_tokens]
+        if len(ent) > BS_ROW_BIAS_MAX:
+            raise BloomStageError(f"{len(ent)} bias / ban entries: a row holds at most {BS_ROW_BIAS_MAX}")
+        p = RowProcessor(float(repetition_penalty), int(no_repeat_ngram), int(min_new_tokens), int(eos_id), len(ent))
+        for i, (t, v) in enumerate(ent):
+            p.bias_ids[i], p.bias_values[i] = t, v
+        return p
+
+    def set_row_processor(self, slot, params=None, count=1, stream=None, **kw):
+        """Give KV rows [slot, slot + count) a logit processor state and empty their token history: `params` is one
+        RowProcessor for all the rows or a sequence of `count`; without it the keywords of row_processor() make one.
+        Stream ordered; captured decode graphs stay."""
+        if params is None:
+            params = self.row_processor(**kw)
+        ps = [params] * count if isinstance(params, RowProcessor) else list(params)
+        if len(ps) != count:
+            raise BloomStageError(f"{len(ps)} processor states for {count} rows")
+        _check(lib().bs_set_row_processor(self._h, int(slot), int(count), (RowProcessor * count)(*ps), stream))
+
+    def clear_row_processor(self, slot=None, count=1, stream=None):
+        """Drop the processor state and the token history of rows [slot, slot + count), or of every row (None)."""
+        if slot is None:
+            slot, count = 0, self.max_batch
+        _check(lib().bs_set_row_processor(self._h, int(slot), int(count), None, stream))
+
+    def note_tokens(self, slot, ids, n=None, generated=False, stream=None):
+        """bs_note_tokens: append tokens to row `slot`'s history (its prompt).  ids: a sequence / numpy array (host,
+        read before the call returns) or a device pointer / torch tensor of n int32 (read on the stream)."""
+        flags = BS_NOTE_GENERATED if generated else 0
+        if isinstance(ids, int) or hasattr(ids, "data_ptr"):
+            n = int(ids.numel() if n is None else n) if hasattr(ids, "data_ptr") else int(n)
+            _check(lib().bs_note_tokens(self._h, int(slot), _ptr(ids), n, flags, stream))
+            return
+        arr = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        _check(lib().bs_note_tokens(self._h, int(slot), arr.ctypes.data, arr.size, flags | BS_STEP_HOST_IO, stream))
+
+    def process_logits(self, logits, slot=0, batch=None, ld=None, stream=None):
+        """bs_process_logits: the tail's apply kernel in place on given logits for rows [slot, slot + batch).  logits: a
+        numpy array [batch][ld] (host I/O; returns the processed copy) or a device pointer / torch tensor (in place)."""
+        if isinstance(logits, np.ndarray):
+            lg = np.array(logits, dtype=np.float32, order="C")
+            lg = lg.reshape(1, -1) if lg.ndim == 1 else lg
+            _check(lib().bs_process_logits(self._h, int(slot), lg.shape[0], lg.ctypes.data, lg.shape[1],
+                                           BS_STEP_HOST_IO, stream))
+            return lg
+        _check(lib().bs_process_logits(self._h, int(slot), int(batch), _ptr(logits), int(ld or self.vocab), 0, stream))
+        return logits
+
+    def read_row_tokens(self, slot):
+        """bs_read_row_tokens: {"tokens": the ordered history (int32), "generated", "distinct"} of row `slot`.
+        Synchronises."""
+        buf = np.empty(self.max_ctx + 1, np.int32)
+        n, g, d = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _check(lib().bs_read_row_tokens(self._h, int(slot), buf.ctypes.data, ctypes.byref(n), ctypes.byref(g),
+                                        ctypes.byref(d)))
+        return {"tokens": buf[:n.value].copy(), "generated": g.value, "distinct": d.value}
 
     def set_graphs(self, on=True):
         """bs_set_graphs: replay captured decode graphs (default) or launch every step eagerly."""

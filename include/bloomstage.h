@@ -385,6 +385,86 @@ int bs_read_row_draw(bs_stage *stage, int32_t slot, bs_row_draw *out);
  * meaning: the row's last plain draw. */
 int bs_read_verify_draw(bs_stage *stage, int32_t slot, int32_t t, bs_row_draw *out);
 
+/* ---- Per-row logit processors: bias, repetition penalty, no-repeat n-gram, banned tokens, minimum new tokens
+ *  ----
+ * Every KV row may hold a processor state: the parameters below plus, on the device, the row's token history T (the
+ * tokens noted with bs_note_tokens, then every token a forward picked for the row, in order), the set of distinct
+ * tokens in it and the count of generated tokens.  Setting, clearing and noting are stream-ordered, do not synchronise
+ * and keep every captured decode graph; a replayed graph applies the rule and records its own pick.
+ *
+ * Rule, on the row's fp32 logits l[0..V) of the position being generated (the values BS_STEP_LOGITS returns), in the
+ * order of transformers' GenerationMixin._get_logits_processor; every step is plain fp32 arithmetic, so given the
+ * logits and T the result is defined bit for bit:
+ *   1 bias      for each entry (token, value) with a finite value, in entry order: l[token] += value (one fp32 add) --
+ *               length-1 sequence_bias.
+ *   2 penalty   r = repetition_penalty (> 0; 1 = off): for each DISTINCT token v of T, once:
+ *               l[v] = l[v] < 0 ? l[v] * r : l[v] / r (an IEEE fp32 multiply or divide; -0.0 < 0 is false).
+ *   3 n-gram    n = no_repeat_ngram (0 = off; 1..32), only if len(T) + 1 >= n: for every i with T[i .. i+n-2] equal to
+ *               the last n-1 tokens of T, ban T[i+n-1].  n = 1 bans every token of T.
+ *   4 bans      an entry whose value is -INFINITY bans its token (length-1 bad_words_ids).
+ *   5 min new   while fewer than min_new_tokens tokens were generated in this row since the state was set, ban eos_id
+ *               (only if eos_id >= 0).
+ * "Ban" stores -FLT_MAX, not -inf: every tail's contract says "all logits finite" and stays true.  For the sampler,
+ * the argument (-FLT_MAX - max l) / temperature is either a large negative finite number or -inf (the subtraction or
+ * the division may overflow for |max l| large or temperature < 1) and never a NaN, because -inf only arises from
+ * finite operands and is never subtracted from or divided by an infinity; expf of either is exactly 0, so a banned
+ * token carries no mass at any temperature > 0 and is never drawn.  A row whose every token is banned picks the first
+ * index (all logits equal).
+ * Not here: frequency / presence penalties, min-p, multi-token sequence_bias and bad_words_ids, and two exclusions with
+ * reasons: beam search (transformers applies the processors to log-softmax scores without
+ * renormalising: another rule) and verify passes (a different seen-set at each position of the pass, and only the
+ * accepted tokens may be noted). */
+#define BS_ROW_BIAS_MAX 64
+typedef struct bs_row_processor {
+  float repetition_penalty;  /* > 0, finite; 1 = off */
+  int32_t no_repeat_ngram;   /* 0 = off, else 1..32 */
+  int32_t min_new_tokens;    /* >= 0 */
+  int32_t eos_id;            /* < 0 = none */
+  int32_t n_bias;            /* entries used below, 0..BS_ROW_BIAS_MAX */
+  int32_t bias_ids[BS_ROW_BIAS_MAX];
+  float bias_values[BS_ROW_BIAS_MAX];  /* finite: added; -INFINITY: the token is banned */
+} bs_row_processor;
+/* Set (params != NULL: [count] states) or clear (params == NULL) the processor state of KV rows [slot, slot + count),
+ * ordered on `stream` (NULL = the stage's own) like a forward.  Either way the rows' token history and generated
+ * counter are emptied, at a cost proportional to the tokens the row had noted, not to vocab.
+ * A bs_forward on the last stage whose rows include at least one row with processor state takes the full head with
+ * its logits written (never the int8 screen; to the caller's logits buffer, or to the shared [max_batch][vocab]
+ * buffer), applies the rule in place, picks with the row sampler's launches (a row without sampler state gets the first
+ * index of its largest logit; a row may hold sampler state, processor state, both or neither) and then appends each
+ * stateful row's pick to its history and counts it as generated -- for seq > 1 too: the first generated token of a
+ * prefill is processed.  BS_STEP_LOGITS then returns the PROCESSED logits, the values the pick saw.  The launches do
+ * not depend on the table's contents (rows without state return at once inside them).  A call with no stateful row is
+ * what it was before, bit for bit, the screened tail included.  bs_forward_score ignores the table; bs_reset_kv,
+ * bs_fork_kv and bs_copy_kv do not touch token state.
+ * BS_ERR_INVALID: repetition_penalty not finite or <= 0, no_repeat_ngram outside [0, 32], min_new_tokens < 0,
+ * eos_id >= vocab, n_bias outside [0, 64], a bias id outside [0, vocab), a NaN or +inf bias value, a bad row range.
+ * BS_ERR_UNSUPPORTED: a classifier, a non-last stage, or a stage without the whole lm_head.  BS_ERR_STATE: setting a
+ * state while bs_set_sampling holds top_k > 1 (and bs_set_sampling(top_k > 1) while a row holds state);
+ * bs_forward_topk, BS_STEP_VERIFY and BS_STEP_VERIFY_DRAW on a row with processor state.
+ * The first call allocates the table, per row an int32 history and distinct list of max_ctx + 1 entries each, a seen
+ * bitmap of ceil(vocab / 32) words and the counters, and, if absent, bs_set_row_sampler's buffers; all counted under
+ * workspace_bytes from then on. */
+int bs_set_row_processor(bs_stage *stage, int32_t slot, int32_t count, const bs_row_processor *params, void *stream);
+/* bs_note_tokens flag: the tokens also count as generated (min_new_tokens). */
+#define BS_NOTE_GENERATED 16
+/* Append n tokens to row `slot`'s history (the prompt, before its prefill pass).  flags & BS_STEP_HOST_IO: ids is a
+ * host pointer, read before the call returns; otherwise a device pointer read on `stream`.  No synchronisation,
+ * captured graphs stay.  BS_ERR_INVALID: the history would exceed max_ctx + 1 tokens (the host keeps the length: every
+ * note, plus one per forward of a row with state), a host id outside [0, vocab), other flags.  BS_ERR_STATE: a row
+ * without processor state.  The device never writes out of bounds whatever the ids are: device-side ids outside
+ * [0, vocab) are dropped. */
+int bs_note_tokens(bs_stage *stage, int32_t slot, const int32_t *ids, int32_t n, int32_t flags, void *stream);
+/* Run the apply kernel -- the one the tail runs -- in place on caller-given fp32 logits [batch][ld] (ld >= vocab;
+ * device, or host with BS_STEP_HOST_IO in flags, then the call synchronises) for rows [slot, slot + batch).  Notes
+ * nothing, touches no KV row.  Statuses as bs_set_row_processor; allocates like it on first use. */
+int bs_process_logits(bs_stage *stage, int32_t slot, int32_t batch, float *logits, int32_t ld, int32_t flags,
+                      void *stream);
+/* Read-out of row `slot`'s token state, for verification (synchronises the device): tokens[0..*n_tokens) = the ordered
+ * history (room for max_ctx + 1; may be NULL), the generated counter and the number of distinct tokens (any may be
+ * NULL).  BS_ERR_STATE on a stage that never used the processors. */
+int bs_read_row_tokens(bs_stage *stage, int32_t slot, int32_t *tokens, int32_t *n_tokens, int32_t *n_generated,
+                       int32_t *n_distinct);
+
 /* Decode steps (S = 1) and BS_STEP_VERIFY passes on device buffers are captured once per shape into a hipGraph and replayed
  * (the default, on = 1); on = 0 launches them eagerly every step (same kernels, same results: for
  * debugging and A/B timing).  Drops captured graphs.  Returns BS_OK.  A stage starts with graphs off
