@@ -17,10 +17,10 @@ LIB = os.path.join(PKG, "lib", "libbloomstage.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "head_score.hip", "attn_verify.hip", "row_sample.hip", "logit_proc.hip", "kv_fork.hip", "beam_topk.hip", "stage.hip", "codec.cpp", "safetensors.cpp"]
+SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "head_score.hip", "attn_verify.hip", "row_sample.hip", "logit_proc.hip", "guide.hip", "kv_fork.hip", "beam_topk.hip", "stage.hip", "codec.cpp", "safetensors.cpp", "guide_table.cpp"]
 # per-source extra flags: the prefill attention keeps its MFMA accumulators in VGPRs (attn_prefill.hip header)
 EXTRA = {"attn_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
-HEADERS = ["common.h", "kernels.h", "attn_merge.h", "safetensors.h", "stage_weights.h"]
+HEADERS = ["common.h", "kernels.h", "attn_merge.h", "safetensors.h", "stage_weights.h", "guide_table.h"]
 STAMP = os.path.join(OBJ, "build_id")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-result", "-Wno-unused-value", f"-I{os.path.join(ROOT, 'include')}"]

@@ -298,6 +298,34 @@ void launch_logit_proc_note_picks(const LogitProcBufs& lp, int slot, int B, cons
 // The rule in place on logits [B][ld] (V columns each) for rows [slot, slot + B); rows without state return at once.
 void launch_logit_proc_apply(const LogitProcBufs& lp, float* logits, int ld, int slot, int B, hipStream_t s);
 
+// ---- Guided decoding (include/bloomstage.h "Guided decoding"; guide.hip) ----
+constexpr int kGuideMax = 16;      // BS_GUIDE_MAX
+constexpr int kGuideSlice = 4096;  // BS_GUIDE_SLICE: vocabulary entries one block of the apply kernel owns
+struct GuideDev {  // one entry of the device table [kGuideMax]; n_states == 0: not loaded
+  const int* row_ptr;       // [n_states + 1]
+  const int* edge_token;    // [edges] strictly ascending inside a state, in [0, V)
+  const int* edge_next;     // [edges] in [-1, n_states)
+  const int* default_next;  // [n_states] in [-1, n_states)
+  int n_states, start;
+};
+struct GuideRowDev { int guide, state, n_steps, n_rejected; };  // one entry per KV row; guide < 0: no state
+struct GuideBufs {
+  GuideDev* guides;   // [kGuideMax]
+  GuideRowDev* rows;  // [max_batch]
+  int V;
+};
+// rows[slot .. slot + n) = {guide, states[i], 0, 0} (states: host, by kernel arguments; guide < 0 clears).  Stream ordered.
+void launch_guide_set(const GuideBufs& gb, int slot, int n, int guide, const int* states, hipStream_t s);
+// The rule in place on logits [B][ld] (V columns each) for rows [slot, slot + B): one launch of a (V slices, B) grid,
+// every logit has one writer; rows without state return at once.
+void launch_guide_apply(const GuideBufs& gb, float* logits, int ld, int slot, int B, hipStream_t s);
+// The tail's advance: row slot + b with state steps by tokens[b]; rows without state return.  One launch.
+void launch_guide_advance_picks(const GuideBufs& gb, int slot, int B, const int* tokens, hipStream_t s);
+// Walk n tokens through row `slot`, in order.  ids_host: read now and passed by kernel arguments (one launch per
+// guide_advance_arg_ids() of them); else ids_dev is read on the stream (one launch).
+void launch_guide_advance(const GuideBufs& gb, int slot, const int* ids_host, const int* ids_dev, int n, hipStream_t s);
+int guide_advance_arg_ids();
+
 // ---- Weight-only int8 (bf16 stages with BS_FLAG_INT8_WEIGHTS; kernels.hip "Weight-only int8") ----
 // Q[n][k] = rne(W[n][k] / scale[n]), scale[n] = max_k |W[n][k]| / 127 (1 for a zero row); W bf16 [N][K].
 void launch_quantize_rows(const void* W_bf16, int8_t* Q, float* scale, int N, int K, hipStream_t s);

@@ -28,6 +28,7 @@
 
 #include "../../include/bloomstage.h"
 #include "common.h"
+#include "guide_table.h"
 #include "kernels.h"
 #include "safetensors.h"
 #include "stage_weights.h"
@@ -83,6 +84,8 @@ enum TailKind {
   TAIL_ROWS,           // full head, per-row sampler (a row of the call holds sampler state)
   TAIL_ROWS_PROC,      // full head with its logits written, the per-row logit processors on them, the per-row sampler as
                        // the pick, the picks noted in the rows' histories (a row of the call holds processor state)
+  TAIL_ROWS_GUIDE,     // TAIL_ROWS_PROC with the guide apply ahead of the pick and the guide advance behind the note (a row
+                       // of the call holds guide state)
   TAIL_TOPK_LOGPROBS,  // bs_forward_topk: full head with its logits written, the k best ids and log-probs of each row
 };
 struct Tail {
@@ -93,7 +96,7 @@ struct Tail {
 
 struct GraphKey {
   int B, seq, slot, flags;
-  TailKind tail;  // row-sampler and row-processor state change the tail of otherwise equal calls: the kind is the
+  TailKind tail;  // row-sampler, row-processor and row-guide state change the tail of otherwise equal calls: the kind is the
                   // key's bit for the route (the setters that change it for every call drop the graphs instead)
   const void* in;
   void* out;
@@ -274,6 +277,15 @@ struct bs_stage {
   struct RowProcHost { int active = 0, len = 0; };
   std::vector<RowProcHost> lp_host;  // [max_batch]
   int lp_active = 0;                 // rows that hold state
+  // guided decoding (guide.hip): the device table of kGuideMax guide descriptors and the rows' guide state, one
+  // allocation made by the first bs_load_guide (gd.guides null: never used); each loaded guide's arrays are one more
+  // allocation, counted as workspace until it is unloaded.  gd_host mirrors the rows' guide ids for routing and for
+  // the reference counts that keep a guide in use from being unloaded
+  GuideBufs gd{};
+  struct GuideHost { void* base = nullptr; int n_states = 0, start = 0, refs = 0; };
+  GuideHost gd_guides[kGuideMax];
+  std::vector<int> gd_host;  // [max_batch] guide id, -1: none
+  int gd_active = 0;         // rows that hold state
   // BS_STEP_VERIFY_DRAW: the sampler scratch of kVerifyMaxTokens positions (vd, made by the first verify-draw pass
   // that runs the sampler) and the [max(max_batch, kVerifyMaxTokens)][V] logits its tail reads when the caller
   // gives no device logits (vd_logits, made by the first such pass); vd_last_*: the shape of the last such pass
@@ -1211,6 +1223,14 @@ static bool rows_processed(const bs_stage* s, int slot, int B) {
   return false;
 }
 
+// Does a row of [slot, slot + B) hold guide state (bs_set_row_guide)?  Then the tail masks before and steps after the pick.
+static bool rows_guided(const bs_stage* s, int slot, int B) {
+  if (!s->gd_active) return false;
+  for (int b = 0; b < B; b++)
+    if (s->gd_host[slot + b] >= 0) return true;
+  return false;
+}
+
 // Which tail this pass ends in (scoring: a bs_forward_score pass).  forward_impl has checked the step against the stage.
 static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring, bool topk = false) {
   const int B = step->batch, M = B * step->seq, V = s->d.vocab;
@@ -1221,7 +1241,8 @@ static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring, bool
   const bool rows = rows_sampled(s, step->slot, B);  // excludes top_k > 1 (bs_set_row_sampler / bs_set_sampling)
   if (step->flags & BS_STEP_VERIFY)
     return Tail{rows && (step->flags & BS_STEP_VERIFY_DRAW) ? TAIL_VERIFY_DRAW : TAIL_VERIFY_ARGMAX, M, V};
-  if (rows_processed(s, step->slot, B)) return Tail{TAIL_ROWS_PROC, B, V};  // forward_impl has excluded verify passes
+  if (rows_guided(s, step->slot, B)) return Tail{TAIL_ROWS_GUIDE, B, V};    // forward_impl has excluded verify passes
+  if (rows_processed(s, step->slot, B)) return Tail{TAIL_ROWS_PROC, B, V};
   if (rows) return Tail{TAIL_ROWS, B, V};
   if (s->top_k > 1) return Tail{TAIL_TOPK, B, V};
   if (s->hs_on && s->hs.Q && !(step->flags & BS_STEP_LOGITS) && head_screen_supported(B, s->d.hidden))
@@ -1456,9 +1477,12 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
     case TAIL_GREEDY:
     case TAIL_TOPK:
     case TAIL_ROWS:
-    case TAIL_ROWS_PROC: {
+    case TAIL_ROWS_PROC:
+    case TAIL_ROWS_GUIDE: {
       // ln_f on each row's last position, tied lm_head, token pick
-      const bool reads_logits = tail.kind == TAIL_TOPK || tail.kind == TAIL_ROWS || tail.kind == TAIL_ROWS_PROC;
+      const bool guided = tail.kind == TAIL_ROWS_GUIDE;
+      const bool processed = tail.kind == TAIL_ROWS_PROC || guided;  // bs_set_row_guide has made the processors' buffers
+      const bool reads_logits = tail.kind == TAIL_TOPK || tail.kind == TAIL_ROWS || processed;
       Epi e{};
       e.kind = EPI_ARGMAX; e.keys = s->keys; e.ldo = V;
       e.key_hi_index = tail.kind == TAIL_TOPK ? 1 : 0;  // sampling ranks equal logits by the higher index (decoding.cpp:44-45)
@@ -1476,12 +1500,16 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
                          s->past_dev, S, st);
       } else {
         linear_ln(s, st, cur, S, S - 1, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
-        if (tail.kind == TAIL_ROWS_PROC)  // in place: BS_STEP_LOGITS returns what the pick saw
+        if (processed)  // in place: BS_STEP_LOGITS returns what the pick saw
           launch_logit_proc_apply(s->lp, e.logits, V, slot, B, st);
-        if (tail.kind == TAIL_ROWS || tail.kind == TAIL_ROWS_PROC)  // rows of the call without state get the first index of their largest logit
+        if (guided)  // after the processors, as prefix_allowed_tokens_fn follows min_new_tokens
+          launch_guide_apply(s->gd, e.logits, V, slot, B, st);
+        if (tail.kind == TAIL_ROWS || processed)  // rows of the call without state get the first index of their largest logit
           launch_row_sample(s->rs, e.logits, V, V, slot, B, nullptr, past_dev, S, tok_out, s->past_dev, st);
-        if (tail.kind == TAIL_ROWS_PROC)  // each row with processor state appends its pick to its history
+        if (processed)  // each row with processor state appends its pick to its history
           launch_logit_proc_note_picks(s->lp, slot, B, tok_out, st);
+        if (guided)  // each row with guide state steps by its pick
+          launch_guide_advance_picks(s->gd, slot, B, tok_out, st);
         if (tail.kind == TAIL_TOPK)
           launch_topk_sample(s->keys, V / 16, e.logits, V, B, s->top_k, 1.0f / s->temperature, s->sample_seed, slot,
                              past_dev, S, tok_out, st, s->past_dev);
@@ -1580,6 +1608,7 @@ extern "C" int bs_set_sampling(bs_stage* s, int32_t top_k, float temperature, ui
   if (top_k > 1 && !(temperature > 0.f)) return fail(BS_ERR_INVALID, "temperature must be positive");
   if (top_k > 1 && s->rs_active) return fail(BS_ERR_STATE, "rows hold per-row sampler state (bs_set_row_sampler)");
   if (top_k > 1 && s->lp_active) return fail(BS_ERR_STATE, "rows hold logit processor state (bs_set_row_processor)");
+  if (top_k > 1 && s->gd_active) return fail(BS_ERR_STATE, "rows hold guide state (bs_set_row_guide)");
   HIP_TRY(hipSetDevice(s->d.device));
   if (top_k > 1 && !s->sample_logits) {
     HIP_TRY(hipStreamSynchronize(s->own));
@@ -1837,6 +1866,179 @@ extern "C" int bs_read_row_tokens(bs_stage* s, int32_t slot, int32_t* tokens, in
   return BS_OK;
 }
 
+// ---- guided decoding (guide.hip)
+static_assert(BS_GUIDE_MAX == kGuideMax && BS_GUIDE_SLICE == kGuideSlice, "guide constants");
+
+static int guide_stage_check(const bs_stage* s) {
+  if (s->n_labels || !s->d.is_last || !s->wemb || s->hv0 != 0 || s->hv1 != s->d.vocab)
+    return fail(BS_ERR_UNSUPPORTED, "guided decoding needs the last stage of a generation model (whole lm_head)");
+  return BS_OK;
+}
+
+// The descriptor table (zeroed: nothing loaded) and the rows' guide state (every row cleared).
+static int guide_buffers(bs_stage* s) {
+  if (s->gd.guides) return BS_OK;
+  const size_t mb = s->d.max_batch;
+  GuideBufs gd{};
+  Carver c;
+  c.piece(&gd.guides, kGuideMax * sizeof(GuideDev));
+  c.piece(&gd.rows, mb * sizeof(GuideRowDev));
+  const int ar = c.alloc(s->own);
+  if (ar == Carver::NO_MEMORY) return fail(BS_ERR_OOM, "guide table allocation failed");
+  if (ar == Carver::NOT_ZEROED) return fail(BS_ERR_DEVICE, "guide table memset");
+  gd.V = s->d.vocab;
+  launch_guide_set(gd, 0, (int)mb, -1, nullptr, s->own);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->own) != hipSuccess) {
+    hipFree(c.base);
+    return fail(BS_ERR_DEVICE, "guide table clear");
+  }
+  s->owned.push_back({c.base, c.total});
+  s->gd = gd;
+  s->gd_host.assign(mb, -1);
+  return BS_OK;
+}
+
+extern "C" int bs_load_guide(bs_stage* s, const bs_guide_desc* g, int32_t* guide_id) {
+  if (!s || !g || !guide_id) return fail(BS_ERR_INVALID, "stage/guide/guide_id is NULL");
+  int rc = guide_stage_check(s);
+  if (rc) return rc;
+  std::string why;
+  if (!guide_table_check(g, s->d.vocab, &why)) return fail(BS_ERR_INVALID, "guide: " + why);
+  int id = 0;
+  while (id < kGuideMax && s->gd_guides[id].base) id++;
+  if (id == kGuideMax) return fail(BS_ERR_STATE, "the stage holds BS_GUIDE_MAX guides already");
+  HIP_TRY(hipSetDevice(s->d.device));
+  if ((rc = guide_buffers(s)) != BS_OK) return rc;
+  const size_t n = g->n_states, ne = g->row_ptr[n];
+  int *row_ptr = nullptr, *tok = nullptr, *next = nullptr, *dn = nullptr;
+  Carver c;
+  c.piece(&row_ptr, (n + 1) * 4);
+  c.piece(&tok, ne * 4);
+  c.piece(&next, ne * 4);
+  c.piece(&dn, n * 4);
+  if (c.alloc() != Carver::OK) return fail(BS_ERR_OOM, "guide allocation failed (" + std::to_string(c.total) + " B)");
+  const GuideDev dev{row_ptr, tok, next, dn, g->n_states, g->start};
+  hipError_t e = hipMemcpy(row_ptr, g->row_ptr, (n + 1) * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && ne) e = hipMemcpy(tok, g->edge_token, ne * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && ne) e = hipMemcpy(next, g->edge_next, ne * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dn, g->default_next, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s->gd.guides + id, &dev, sizeof(dev), hipMemcpyHostToDevice);  // last: the arrays are in place
+  if (e != hipSuccess) {
+    hipFree(c.base);
+    return fail(BS_ERR_DEVICE, std::string("guide copy: ") + hipGetErrorString(e));
+  }
+  s->owned.push_back({c.base, (2 * n + 1 + 2 * ne) * 4});
+  s->gd_guides[id] = bs_stage::GuideHost{c.base, g->n_states, g->start, 0};
+  *guide_id = id;
+  return BS_OK;
+}
+
+extern "C" int bs_unload_guide(bs_stage* s, int32_t id) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (id < 0 || id >= kGuideMax || !s->gd_guides[id].base) return fail(BS_ERR_STATE, "no such guide is loaded");
+  if (s->gd_guides[id].refs) return fail(BS_ERR_STATE, "a row still references the guide (bs_set_row_guide clears it)");
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());  // launches that read the guide have finished
+  const GuideDev none{};
+  HIP_TRY(hipMemcpy(s->gd.guides + id, &none, sizeof(none), hipMemcpyHostToDevice));
+  void* base = s->gd_guides[id].base;
+  s->owned.erase(std::find_if(s->owned.begin(), s->owned.end(), [&](const OwnedAlloc& a) { return a.p == base; }));
+  s->gd_guides[id] = bs_stage::GuideHost{};
+  HIP_TRY(hipFree(base));
+  return BS_OK;
+}
+
+extern "C" int bs_set_row_guide(bs_stage* s, int32_t slot, int32_t count, int32_t id, const int32_t* states, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  int rc = guide_stage_check(s);
+  if (rc) return rc;
+  if (count <= 0 || slot < 0 || slot > s->d.max_batch - count) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  const bool set = id >= 0;
+  if (set && (id >= kGuideMax || !s->gd_guides[id].base)) return fail(BS_ERR_STATE, "no such guide is loaded");
+  if (set && s->top_k > 1) return fail(BS_ERR_STATE, "bs_set_sampling holds top_k > 1");
+  if (!set && !s->gd.guides) return BS_OK;  // nothing was ever loaded
+  std::vector<int> st(count, set ? s->gd_guides[id].start : 0);
+  for (int i = 0; set && states && i < count; i++) {
+    if (states[i] < 0 || states[i] >= s->gd_guides[id].n_states) return fail(BS_ERR_INVALID, "state outside the guide");
+    st[i] = states[i];
+  }
+  HIP_TRY(hipSetDevice(s->d.device));
+  if (set && (rc = logit_proc_buffers(s)) != BS_OK) return rc;  // the route runs the processors' and the sampler's launches
+  launch_guide_set(s->gd, slot, count, set ? id : -1, st.data(), stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("guide row table: ") + hipGetErrorString(err));
+  for (int i = 0; i < count; i++) {
+    int& cur = s->gd_host[slot + i];
+    if (cur >= 0) { s->gd_guides[cur].refs--; s->gd_active--; }
+    cur = set ? id : -1;
+    if (set) { s->gd_guides[id].refs++; s->gd_active++; }
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_advance_row_guide(bs_stage* s, int32_t slot, const int32_t* ids, int32_t n, int32_t flags, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot out of range");
+  if (flags & ~BS_STEP_HOST_IO) return fail(BS_ERR_INVALID, "only BS_STEP_HOST_IO is valid here");
+  if (n < 0 || (n > 0 && !ids)) return fail(BS_ERR_INVALID, "bad ids / n");
+  if (!s->gd.guides || s->gd_host[slot] < 0) return fail(BS_ERR_STATE, "the row holds no guide state");
+  const bool host = (flags & BS_STEP_HOST_IO) != 0;
+  if (host)
+    for (int i = 0; i < n; i++)
+      if (ids[i] < 0 || ids[i] >= s->d.vocab) return fail(BS_ERR_INVALID, "token id out of range");
+  if (n == 0) return BS_OK;
+  HIP_TRY(hipSetDevice(s->d.device));
+  launch_guide_advance(s->gd, slot, host ? ids : nullptr, host ? nullptr : ids, n, stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("guide advance: ") + hipGetErrorString(err));
+  return BS_OK;
+}
+
+extern "C" int bs_guide_logits(bs_stage* s, int32_t slot, int32_t batch, float* logits, int32_t ld, int32_t flags,
+                               void* stream) {
+  if (!s || !logits) return fail(BS_ERR_INVALID, "stage/logits is NULL");
+  int rc = guide_stage_check(s);
+  if (rc) return rc;
+  const int V = s->d.vocab;
+  if (batch <= 0 || slot < 0 || slot > s->d.max_batch - batch) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (ld < V) return fail(BS_ERR_INVALID, "ld must be >= vocab");
+  if (flags & ~BS_STEP_HOST_IO) return fail(BS_ERR_INVALID, "only BS_STEP_HOST_IO is valid here");
+  if (!s->gd.guides) return fail(BS_ERR_STATE, "the stage never loaded a guide");
+  HIP_TRY(hipSetDevice(s->d.device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  const bool host_io = (flags & BS_STEP_HOST_IO) != 0;
+  float* dl = logits;
+  const size_t n = (size_t)(batch - 1) * ld + V;  // the last row may end at its V-th column
+  if (host_io) {
+    if ((rc = logits_staging(s, (size_t)batch * ld * 4, st, &dl)) != BS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(dl, logits, n * 4, hipMemcpyHostToDevice, st));
+  }
+  launch_guide_apply(s->gd, dl, ld, slot, batch, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("guide apply: ") + hipGetErrorString(err));
+  if (host_io) {
+    HIP_TRY(hipMemcpyAsync(logits, dl, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_read_row_guide(bs_stage* s, int32_t slot, int32_t* guide_id, int32_t* state, int32_t* n_steps,
+                                 int32_t* n_rejected) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot out of range");
+  if (!s->gd.guides) return fail(BS_ERR_STATE, "the stage never loaded a guide");
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());
+  GuideRowDev r;
+  HIP_TRY(hipMemcpy(&r, s->gd.rows + slot, sizeof(r), hipMemcpyDeviceToHost));
+  if (guide_id) *guide_id = r.guide < 0 ? -1 : r.guide;
+  if (state) *state = r.state;
+  if (n_steps) *n_steps = r.n_steps;
+  if (n_rejected) *n_rejected = r.n_rejected;
+  return BS_OK;
+}
+
 // The scratch of a verify-draw pass (first use) and, when the pass has no other device logits to write, its own
 // logits buffer (first such use).
 static int verify_draw_buffers(bs_stage* s, bool need_logits) {
@@ -1966,6 +2168,8 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   if (tk && rows_sampled(s, slot, B)) return fail(BS_ERR_STATE, "bs_forward_topk on a row that holds sampler state");
   if (!sc && (tk || verify) && rows_processed(s, slot, B))
     return fail(BS_ERR_STATE, "bs_forward_topk / BS_STEP_VERIFY on a row that holds logit processor state");
+  if (!sc && (tk || verify) && rows_guided(s, slot, B))
+    return fail(BS_ERR_STATE, "bs_forward_topk / BS_STEP_VERIFY on a row that holds guide state");
   const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
   if (want_logits && (!d.is_last || !logits)) return fail(BS_ERR_INVALID, "logits requested on a non-last stage or NULL");
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
@@ -2046,7 +2250,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
   s->hs_last_rows = tail.kind == TAIL_SCREENED ? B : 0;
   if (tail.kind == TAIL_VERIFY_DRAW) { s->vd_last_slot = slot; s->vd_last_B = B; s->vd_last_S = S; }
-  if (tail.kind == TAIL_ROWS_PROC)  // the note launch appended one pick to every row with state
+  if (tail.kind == TAIL_ROWS_PROC || tail.kind == TAIL_ROWS_GUIDE)  // the note launch appended one pick to every row with state
     for (int b = 0; b < B; b++)
       if (s->lp_host[slot + b].active) s->lp_host[slot + b].len = std::min(s->lp_host[slot + b].len + 1, s->lp.cap);
   if (d.is_last) {  // the last kernel advanced past_dev[0..B) by S (stream-ordered before the next forward)

@@ -116,6 +116,20 @@ class StageExecutor:
             return
         self._run(call, ())
 
+    def set_row_guide(self, slot, guide_id=None):
+        """Stage.set_row_guide of KV row `slot` at the guide's start state, or clear_row_guide (None), ordered like
+        forward."""
+        def call(h):
+            if guide_id is None:
+                self.stage.clear_row_guide(slot, 1, stream=h)
+            else:
+                self.stage.set_row_guide(slot, guide_id, stream=h)
+        sh = self._sh if self._sh is not None else torch.cuda.current_stream().cuda_stream
+        if sh:
+            call(sh)
+            return
+        self._run(call, ())
+
     def fork_kv(self, src, dst, npos, count=1):
         """Stage.fork_kv: positions [0, npos) of KV row `src` copied to rows [dst, dst + count), ordered like
         forward."""
@@ -411,6 +425,21 @@ class Pipeline:
             if self.head_split:
                 raise ValueError("logit processors need the whole lm_head on the last stage: build_rank(sample=True)")
             self.ex.set_row_processor(mb * self.mb + row, prompt=prompt, **state)
+
+    def load_guide(self, guide):
+        """Guided decoding (bs_load_guide): the last rank copies the token automaton to its stage and returns the
+        guide's id; None elsewhere.  Needs the whole lm_head on the last stage (build_rank(..., sample=True))."""
+        if not self.is_last:
+            return None
+        if self.head_split:
+            raise ValueError("guided decoding needs the whole lm_head on the last stage: build_rank(sample=True)")
+        return self.ex.stage.load_guide(guide)
+
+    def set_row_guide(self, mb, row, guide_id=None):
+        """Give row `row` of micro-batch `mb` the guide at its start state (bs_set_row_guide), or clear it (None).
+        Acts on the last rank, ordered with its forwards; a no-op elsewhere."""
+        if self.is_last:
+            self.ex.set_row_guide(mb * self.mb + row, guide_id)
 
     def finish(self, record=None):
         """Rank 0 collects the tokens of the last round; everyone drains its sends.  Later steps

@@ -63,6 +63,13 @@ token history, just before the prefill pass that yields the first generated toke
 own picks.  The last rank holds the prompts (they are broadcast once at start when world > 1) and the whole lm_head.
 They combine with --sample (the processed logits are what the sampler draws from), --shared-prefix, --kv int8 and
 int8 / MXFP4 weights.
+--guide-file PATH (a JSON token automaton, guide.Guide.to_json) or --choice "ID,ID,..." (repeatable, with --eos-id: the
+sample generates exactly one of the sequences, then only the EOS) is guided decoding (bs_set_row_guide, DESIGN.md §5k;
+transformers' prefix_allowed_tokens_fn): the last rank loads the guide once and, at admission, sets the sample's row to
+the guide's start state just before the prefill pass, so the guide sees generated tokens only (never the prompt or a
+shared prefix); from then on the device masks the logits ahead of the pick and steps the state behind it.  Each
+sample's record gains the guide's final state, the count of rejected picks and the index of the first EOS.  Combines
+with --sample, the logit processor options, --shared-prefix, --kv int8 and int8 / MXFP4 weights.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
 unseeded top-k, token ids in (no tokenizer).
@@ -121,6 +128,19 @@ class RunConfig:
     min_new_tokens: int = 0           # logit processors: eos_id is banned for a sample's first min_new_tokens tokens
     bad_token: tuple = ()             # logit processors: banned token ids (at most 64 with token_bias)
     token_bias: tuple = ()            # logit processors: (id, value) pairs or "ID:VALUE" strings, value added to the logit
+    guide_file: str = ""              # guided decoding: a JSON token automaton (guide.Guide.to_json) for every sample
+    choice: tuple = ()                # guided decoding: token-id sequences ("ID,ID,..." or lists), one is generated, then eos_id
+
+    @property
+    def guided(self):
+        return bool(self.guide_file or self.choice)
+
+    def make_guide(self, vocab):
+        """The run's Guide (None when guided decoding is off), validated against the vocabulary."""
+        from . import guide
+        if self.choice:
+            return guide.from_choices(self.choice, self.eos_id).validate(vocab)
+        return guide.Guide.from_file(self.guide_file).validate(vocab) if self.guide_file else None
 
     @property
     def processors(self):
@@ -138,6 +158,20 @@ class RunConfig:
         self.bad_token = tuple(int(t) for t in self.bad_token)
         self.token_bias = tuple((int(str(e).split(":")[0]), float(str(e).split(":")[1])) if isinstance(e, str)
                                 else (int(e[0]), float(e[1])) for e in self.token_bias)
+        self.choice = tuple(tuple(int(t) for t in (c.split(",") if isinstance(c, str) else c)) for c in self.choice)
+        if self.guided:
+            if (self.speculate or self.sample_speculate or self.num_beams or self.score or self.max_length <= 0
+                    or not self.prefill):
+                raise ValueError("guided decoding (guide_file, choice) is plain generation with admission prefills: it "
+                                 "excludes speculate, sample_speculate, num_beams, score, max_length == 0 and "
+                                 "prefill = False")
+            if self.guide_file and self.choice:
+                raise ValueError("guide_file and choice exclude each other")
+            if self.choice and self.eos_id < 0:
+                raise ValueError("choice needs eos_id, the token that follows a finished choice")
+            if any(len(c) == 0 or min(c) < 0 for c in self.choice):
+                raise ValueError("a choice is a non-empty sequence of token ids")
+            self.head_split = False  # the whole lm_head on the last stage, as for sample
         if self.processors:
             if (self.speculate or self.sample_speculate or self.num_beams or self.score or self.max_length <= 0
                     or not self.prefill):
@@ -258,6 +292,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     proc = cfg.processors
     if proc and executor_factory is not None:
         raise ValueError("the logit processors are the HIP stage's: not available with an executor_factory")
+    if cfg.guided and executor_factory is not None:
+        raise ValueError("guided decoding is the HIP stage's: not available with an executor_factory")
     if cfg.num_sample < 1 or cfg.max_length < 0 or cfg.core_pool_size < 1:
         raise ValueError("num_sample and core_pool_size must be >= 1, max_length >= 0 (0: classification)")
     model = config.get(cfg.model) if isinstance(cfg.model, str) else cfg.model
@@ -301,6 +337,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
                 for n in lens:
                     prompts.append(flat[at:at + n])
                     at += n
+    guide = cfg.make_guide(model.vocab)  # every rank reads it; the last loads it, rank 0 walks the results through it
     if cfg.score:
         return _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.max_length == 0:
@@ -343,7 +380,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + cfg.max_length + 1, max_seq=max_seq, seed=cfg.seed,
                                 head_split=cfg.head_split, executor_factory=executor_factory,
-                                kv_int8=cfg.kv == "int8", sample=cfg.sample or bool(proc), extra_rows=int(fork))
+                                kv_int8=cfg.kv == "int8", sample=cfg.sample or bool(proc) or cfg.guided,
+                                extra_rows=int(fork))
+    guide_id = pipe.load_guide(guide) if guide is not None else None  # once, outside the decode loop (last rank)
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "rounds": T, "prefill": pf,
                     **({"shared_prefix": P, "prefix_fork": fork} if P else {})})
@@ -385,6 +424,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
             if proc and rank == world - 1:  # the row's processor state and its history, the whole prompt (a forked or
                 # prefilled prefix included), ordered before the pass whose tail yields the first generated token
                 pipe.set_row_processor(r // mb, r % mb, prompt=prompts[i], **proc)
+            if guide is not None:  # the start state, ordered before that pass: the guide sees generated tokens only
+                pipe.set_row_guide(r // mb, r % mb, guide_id)
             if P:  # the rest of the prompt behind the prefix; its tail yields the first generated token
                 tok = pipe.prefill_row(r // mb, r % mb, rest[i], lens[i] - P, past=P)
             else:
@@ -424,6 +465,15 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     if proc:
         res.update(processors={k: v for k, v in proc.items() if k not in ("bias", "bad_tokens")},
                    token_bias=[list(e) for e in cfg.token_bias], bad_token=list(cfg.bad_token))
+    if guide is not None:  # per sample: the state its tokens lead to, the picks the guide rejected, the first EOS (the
+        # host's walk of the sample's tokens: a row's device state is overwritten at the next admission and goes on
+        # stepping while the row idles)
+        recs = []
+        for o in out:
+            q, rej = guide.walk(o)
+            recs.append({"state": q, "n_rejected": rej, "eos_at": o.index(cfg.eos_id) if cfg.eos_id in o else None})
+        res.update(guide={"n_states": int(guide.n_states), "choice": [list(c) for c in cfg.choice],
+                          "guide_file": cfg.guide_file, "eos_id": cfg.eos_id}, guide_records=recs)
     if P:  # prefill_tokens: the tokens pushed through prefill passes, the template's included
         res.update(shared_prefix=P, prefix_fork=fork, prefill_tokens=prefill_tokens)
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})
@@ -634,7 +684,7 @@ def main(argv=None):
     for f in dataclasses.fields(RunConfig):
         flag = "--" + f.name.replace("_", "-")
         if f.type is tuple or f.type == "tuple":  # repeatable: --bad-token ID, --token-bias ID:VALUE
-            p.add_argument(flag, action="append", default=[], type=int if f.name == "bad_token" else str)
+            p.add_argument(flag, action="append", default=[], type=int if f.name == "bad_token" else str)  # and --choice
         elif f.type is bool or f.type == "bool":
             p.add_argument(flag, type=int, nargs="?", const=1, default=int(f.default))  # `--score` == `--score 1`
         else:

@@ -43,6 +43,8 @@ BS_STEP_VERIFY = 4        # bs_step.flags: short verify pass (2 <= seq <= 8), gr
 BS_STEP_VERIFY_DRAW = 8   # bs_step.flags, with BS_STEP_VERIFY: the row sampler's draw at every position
 BS_NOTE_GENERATED = 16    # bs_note_tokens flags: the noted tokens also count as generated
 BS_ROW_BIAS_MAX = 64
+BS_GUIDE_MAX = 16         # guides a stage holds at a time
+BS_GUIDE_SLICE = 4096     # vocabulary entries one block of the guide apply kernel owns
 BS_FLAG_INT8_WEIGHTS = 1  # bs_stage_desc.flags: weight-only int8 block matrices
 BS_FLAG_CLASSIFIER = 2    # bs_stage_desc.flags: sequence-classification tail (score head, class ids out)
 BS_FLAG_INT8_KV = 4       # bs_stage_desc.flags: int8 KV cache, one fp32 scale per (position, head) vector
@@ -93,6 +95,13 @@ class RowProcessor(ctypes.Structure):
                 ("bias_ids", ctypes.c_int32 * BS_ROW_BIAS_MAX), ("bias_values", ctypes.c_float * BS_ROW_BIAS_MAX)]
 
 
+class GuideDesc(ctypes.Structure):
+    """bs_guide_desc: a token automaton in CSR form (host arrays)."""
+    _fields_ = [("n_states", ctypes.c_int32), ("start", ctypes.c_int32),
+                ("row_ptr", ctypes.POINTER(ctypes.c_int32)), ("edge_token", ctypes.POINTER(ctypes.c_int32)),
+                ("edge_next", ctypes.POINTER(ctypes.c_int32)), ("default_next", ctypes.POINTER(ctypes.c_int32))]
+
+
 class RowDraw(ctypes.Structure):
     """bs_row_draw: read-out of a row's last draw."""
     _fields_ = [("threshold", ctypes.c_float), ("n_nucleus", ctypes.c_int32), ("n_candidates", ctypes.c_int32),
@@ -115,6 +124,8 @@ EXPORTS = [
     "bs_forward_score", "bs_set_row_sampler", "bs_sample_logits", "bs_read_row_draw",
     "bs_read_verify_draw", "bs_fork_kv", "bs_copy_kv", "bs_forward_topk",
     "bs_set_row_processor", "bs_note_tokens", "bs_process_logits", "bs_read_row_tokens",
+    "bs_load_guide", "bs_unload_guide", "bs_set_row_guide", "bs_advance_row_guide", "bs_guide_logits",
+    "bs_read_row_guide",
 ]
 
 _LIB = None
@@ -179,6 +190,12 @@ def lib():
         L.bs_note_tokens.argtypes = [vp, i32, vp, i32, i32, vp]
         L.bs_process_logits.argtypes = [vp, i32, i32, vp, i32, i32, vp]
         L.bs_read_row_tokens.argtypes = [vp, i32, vp] + [ctypes.POINTER(i32)] * 3
+        L.bs_load_guide.argtypes = [vp, ctypes.POINTER(GuideDesc), ctypes.POINTER(i32)]
+        L.bs_unload_guide.argtypes = [vp, i32]
+        L.bs_set_row_guide.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.bs_advance_row_guide.argtypes = [vp, i32, vp, i32, i32, vp]
+        L.bs_guide_logits.argtypes = [vp, i32, i32, vp, i32, i32, vp]
+        L.bs_read_row_guide.argtypes = [vp, i32] + [ctypes.POINTER(i32)] * 4
         L.bs_set_graphs.argtypes = [vp, i32]
         L.bs_set_head_screen.argtypes = [vp, i32]
         L.bs_read_head_screen.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(i32)]
@@ -512,6 +529,70 @@ class Stage:
         _check(lib().bs_read_row_tokens(self._h, int(slot), buf.ctypes.data, ctypes.byref(n), ctypes.byref(g),
                                         ctypes.byref(d)))
         return {"tokens": buf[:n.value].copy(), "generated": g.value, "distinct": d.value}
+
+    # ---- guided decoding (bs_load_guide; last stage of a generation model)
+    def load_guide(self, guide):
+        """bs_load_guide: copy a token automaton to the device and return its id.  `guide`: anything with n_states,
+        start, row_ptr, edge_token, edge_next and default_next (guide.Guide), or a dict of them.  May synchronise."""
+        get = guide.__getitem__ if isinstance(guide, dict) else lambda k: getattr(guide, k)
+        arrs = [np.ascontiguousarray(get(k), dtype=np.int32).reshape(-1)
+                for k in ("row_ptr", "edge_token", "edge_next", "default_next")]
+        ip = ctypes.POINTER(ctypes.c_int32)
+        d = GuideDesc(int(get("n_states")), int(get("start")), *[a.ctypes.data_as(ip) for a in arrs])
+        gid = ctypes.c_int32(-1)
+        _check(lib().bs_load_guide(self._h, ctypes.byref(d), ctypes.byref(gid)))
+        return gid.value
+
+    def unload_guide(self, guide_id):
+        """bs_unload_guide: free a guide no row references.  Synchronises."""
+        _check(lib().bs_unload_guide(self._h, int(guide_id)))
+
+    def set_row_guide(self, slot, guide_id, states=None, count=1, stream=None):
+        """bs_set_row_guide: give KV rows [slot, slot + count) the guide and a state each (`states`: one int for all
+        the rows, a sequence of `count`, or None for the guide's start state) and zero their counters.  Stream ordered;
+        captured decode graphs stay."""
+        st = None
+        if states is not None:
+            st = np.ascontiguousarray([states] * count if np.isscalar(states) else states, dtype=np.int32).reshape(-1)
+            if st.size != count:
+                raise BloomStageError(f"{st.size} guide states for {count} rows")
+        _check(lib().bs_set_row_guide(self._h, int(slot), int(count), int(guide_id),
+                                      None if st is None else st.ctypes.data, stream))
+
+    def clear_row_guide(self, slot=None, count=1, stream=None):
+        """Drop the guide state of rows [slot, slot + count), or of every row (None)."""
+        if slot is None:
+            slot, count = 0, self.max_batch
+        _check(lib().bs_set_row_guide(self._h, int(slot), int(count), -1, None, stream))
+
+    def advance_row_guide(self, slot, ids, n=None, stream=None):
+        """bs_advance_row_guide: walk tokens through row `slot`'s guide state.  ids: a sequence / numpy array (host, read
+        before the call returns) or a device pointer / torch tensor of n int32 (read on the stream)."""
+        if isinstance(ids, int) or hasattr(ids, "data_ptr"):
+            n = int(ids.numel() if n is None else n) if hasattr(ids, "data_ptr") else int(n)
+            _check(lib().bs_advance_row_guide(self._h, int(slot), _ptr(ids), n, 0, stream))
+            return
+        arr = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        _check(lib().bs_advance_row_guide(self._h, int(slot), arr.ctypes.data, arr.size, BS_STEP_HOST_IO, stream))
+
+    def guide_logits(self, logits, slot=0, batch=None, ld=None, stream=None):
+        """bs_guide_logits: the tail's guide apply kernel in place on given logits for rows [slot, slot + batch).
+        logits: a numpy array [batch][ld] (host I/O; returns the masked copy) or a device pointer / torch tensor."""
+        if isinstance(logits, np.ndarray):
+            lg = np.array(logits, dtype=np.float32, order="C")
+            lg = lg.reshape(1, -1) if lg.ndim == 1 else lg
+            _check(lib().bs_guide_logits(self._h, int(slot), lg.shape[0], lg.ctypes.data, lg.shape[1],
+                                         BS_STEP_HOST_IO, stream))
+            return lg
+        _check(lib().bs_guide_logits(self._h, int(slot), int(batch), _ptr(logits), int(ld or self.vocab), 0, stream))
+        return logits
+
+    def read_row_guide(self, slot):
+        """bs_read_row_guide: {"guide", "state", "n_steps", "n_rejected"} of row `slot` (guide -1: none).
+        Synchronises."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        _check(lib().bs_read_row_guide(self._h, int(slot), *[ctypes.byref(x) for x in v]))
+        return dict(zip(("guide", "state", "n_steps", "n_rejected"), (x.value for x in v)))
 
     def set_graphs(self, on=True):
         """bs_set_graphs: replay captured decode graphs (default) or launch every step eagerly."""

@@ -465,6 +465,80 @@ int bs_process_logits(bs_stage *stage, int32_t slot, int32_t batch, float *logit
 int bs_read_row_tokens(bs_stage *stage, int32_t slot, int32_t *tokens, int32_t *n_tokens, int32_t *n_generated,
                        int32_t *n_distinct);
 
+/* ---- Guided decoding: per-row token automata ----
+ * A guide is a DFA over token ids in CSR form: state q owns the edges row_ptr[q] .. row_ptr[q + 1), each a token
+ * (strictly ascending inside a state) and a next state, and a default next state for every other token:
+ *   step(q, v)  = edge_next[e] if q has an edge e with edge_token[e] == v, else default_next[q]
+ *   v is ALLOWED in q  iff  step(q, v) >= 0
+ * A state that allows a handful of tokens has default_next = -1 and a few edges; a state that allows nearly the whole
+ * vocabulary has default_next >= 0 and edges with edge_next = -1 for the explicit bans.  This is transformers'
+ * prefix_allowed_tokens_fn, and what guided-decoding front ends make of a regex or a JSON schema and a tokenizer.
+ *
+ * Every KV row may hold a guide state (guide id, state q, two counters) on the device.  Rule, on the row's fp32 logits
+ * l[0..V) of the position being generated, after step 5 of the processor rule above and before the pick (transformers'
+ * order: prefix_allowed_tokens_fn follows min_new_tokens): every v that is not allowed in q gets l[v] = -FLT_MAX (the
+ * processors' "ban": all logits stay finite and a banned token carries no sampler mass at any temperature); allowed
+ * logits are not touched, bit for bit.  After the pick t the row's state becomes step(q, t) if t is allowed; otherwise
+ * it stays q and the row's n_rejected counter goes up (only possible when the processors banned every allowed token and
+ * the pick fell to the first index).  n_steps counts both.  Given the logits and q the result is defined bit for bit.
+ * Multi-token bad_words_ids are expressible as a guide.  Not here: guides in verify passes and in beam search
+ * (BS_ERR_STATE, for the processors' reasons). */
+#define BS_GUIDE_MAX 16               /* guides a stage holds at a time */
+#define BS_GUIDE_MAX_STATES (1 << 20)
+#define BS_GUIDE_SLICE 4096           /* vocabulary entries one block of the apply kernel owns */
+typedef struct bs_guide_desc {
+  int32_t n_states;             /* 1 .. BS_GUIDE_MAX_STATES */
+  int32_t start;                /* 0 .. n_states - 1 */
+  const int32_t *row_ptr;       /* [n_states + 1], row_ptr[0] = 0, non-decreasing */
+  const int32_t *edge_token;    /* [row_ptr[n_states]], in [0, vocab), strictly ascending inside a state */
+  const int32_t *edge_next;     /* [row_ptr[n_states]], in [-1, n_states) */
+  const int32_t *default_next;  /* [n_states], in [-1, n_states) */
+} bs_guide_desc;
+/* Load a guide (host arrays, copied to the device; may synchronise: meant to run outside the decode loop) and return
+ * its id in *guide_id (0 .. BS_GUIDE_MAX - 1); unload frees it.  The kernels read guides through a fixed device table of
+ * BS_GUIDE_MAX descriptors, so loading and unloading keep every captured graph.  The tables are validated on the host
+ * before anything is allocated, BS_ERR_INVALID with a message that names the offending state: n_states outside
+ * [1, 2^20], start out of range, row_ptr not starting at 0 or decreasing, tokens not strictly ascending inside a state
+ * or outside [0, vocab), a next state outside [-1, n_states), a state that allows no token.  The first load also makes
+ * the descriptor table and the rows' guide state (16 B a row); a guide's arrays (4 * (2 * n_states + 1 + 2 * edges)
+ * bytes) are counted under workspace_bytes from load to unload.  BS_ERR_STATE: a 17th guide; unloading a guide a row
+ * still references, or an id that is not loaded.  BS_ERR_UNSUPPORTED: a classifier, a non-last stage, or a stage
+ * without the whole lm_head. */
+int bs_load_guide(bs_stage *stage, const bs_guide_desc *guide, int32_t *guide_id);
+int bs_unload_guide(bs_stage *stage, int32_t guide_id);
+/* Give KV rows [slot, slot + count) guide `guide_id` and a state each (states[count], host, read before the call
+ * returns and passed as kernel arguments; NULL: the guide's start state), or clear them (guide_id = -1).  Either way
+ * the rows' n_steps and n_rejected counters are zeroed.  Ordered on `stream` (NULL = the stage's own) like a forward;
+ * no synchronisation, captured graphs stay.
+ * A bs_forward on the last stage whose rows include at least one guided row runs the processors' route with two
+ * launches added: the full head with its logits written, the processors' apply, the guide apply, the row sampler's
+ * launches as the pick, the processors' note, the guide advance.  A row may hold any subset of sampler, processor and
+ * guide state.  BS_STEP_LOGITS returns what the pick saw; seq > 1 works (the first generated token of a prefill is
+ * guided from the row's current state).  A call with no guided row enqueues what it did before.  bs_forward_score
+ * ignores guides; bs_reset_kv, bs_fork_kv and bs_copy_kv do not touch guide state.  The first set allocates, if absent,
+ * the buffers of bs_set_row_sampler and bs_set_row_processor (their launches are part of the route).
+ * BS_ERR_INVALID: a bad row range, a state outside the guide.  BS_ERR_STATE: a guide id that is not loaded; setting
+ * while bs_set_sampling holds top_k > 1 (and bs_set_sampling(top_k > 1) while a row is guided); bs_forward_topk,
+ * BS_STEP_VERIFY and BS_STEP_VERIFY_DRAW on a guided row.  BS_ERR_UNSUPPORTED as bs_load_guide. */
+int bs_set_row_guide(bs_stage *stage, int32_t slot, int32_t count, int32_t guide_id, const int32_t *states,
+                     void *stream);
+/* Walk n tokens through row `slot`'s state, in order, with the step rule: a token that is not allowed leaves the state
+ * and counts as rejected (forced prefixes; re-entry after a caller-side rollback).  flags & BS_STEP_HOST_IO: ids is a
+ * host pointer, read before the call returns (the ids travel as kernel arguments); otherwise a device pointer read on
+ * `stream`, where an id outside [0, vocab) is rejected.  No synchronisation, captured graphs stay.  BS_ERR_INVALID: a
+ * host id outside [0, vocab), other flags.  BS_ERR_STATE: the row is not guided. */
+int bs_advance_row_guide(bs_stage *stage, int32_t slot, const int32_t *ids, int32_t n, int32_t flags, void *stream);
+/* Run the guide apply kernel -- the one the tail runs -- in place on caller-given fp32 logits [batch][ld] (ld >= vocab;
+ * device, or host with BS_STEP_HOST_IO in flags, then the call synchronises) for rows [slot, slot + batch).  Advances
+ * nothing.  Rows whose base address is 16-byte aligned take 16-byte stores, others 4-byte ones.  BS_ERR_STATE on a
+ * stage that never loaded a guide. */
+int bs_guide_logits(bs_stage *stage, int32_t slot, int32_t batch, float *logits, int32_t ld, int32_t flags,
+                    void *stream);
+/* Read-out of row `slot`'s guide state, for verification (synchronises the device): the guide id (-1: none), the state
+ * and the two counters (any may be NULL).  BS_ERR_STATE on a stage that never loaded a guide. */
+int bs_read_row_guide(bs_stage *stage, int32_t slot, int32_t *guide_id, int32_t *state, int32_t *n_steps,
+                      int32_t *n_rejected);
+
 /* Decode steps (S = 1) and BS_STEP_VERIFY passes on device buffers are captured once per shape into a hipGraph and replayed
  * (the default, on = 1); on = 0 launches them eagerly every step (same kernels, same results: for
  * debugging and A/B timing).  Drops captured graphs.  Returns BS_OK.  A stage starts with graphs off
