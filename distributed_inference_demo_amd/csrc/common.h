@@ -17,6 +17,18 @@ template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16 from_f32<bf16>(float v) { return (bf16)v; }  // RNE (v_cvt_pk_bf16_f32)
 
+// A lane offset of zero the compiler cannot see through.  A load whose address is the same in every lane
+// (p[0], p[blockIdx.x]) is compiled to a scalar load, and the wave then waits for its result (lgkmcnt(0)) at
+// the next use of any SGPR it feeds or at the end of the basic block -- a whole memory round trip before the
+// loads behind it are even issued.  p[i + lane_zero()] stays a vector load: it is issued beside the other
+// vector loads and waited for (vmcnt, in order) only where its value is used.  For loads on a kernel's path to
+// its first stream only; everywhere else the scalar load is the cheaper instruction.
+__device__ __forceinline__ int lane_zero() {
+  int z;
+  asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+  return z;
+}
+
 // Wave reductions without LDS: DPP butterflies inside each 16-lane row (xor 1, xor 2, rotate 4,
 // rotate 8), then the four row results through v_readlane.  Every lane returns the total.
 // (__shfl_xor lowers to ds_bpermute: six LDS round trips per reduction.)

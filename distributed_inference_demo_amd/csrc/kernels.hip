@@ -194,10 +194,12 @@ __device__ __forceinline__ void epi_store(const Epi& e, int m, int n, float v) {
 // Epilogue operands that do not depend on the GEMV result (bias, residual, past_len): a GEMV whose
 // output lane is known up front loads them at kernel start, so the epilogue is not one more memory
 // round trip after the reduction (decode GEMVs are latency-bound; each round trip is ~1 us).
+// In the generated code (tools/decode_prologue_isa.py prints it) all three are vector loads issued
+// after the kernel's one argument wait, with no wait between them and the first weight load.
 struct EpiPre {
   uint32_t bias_bits;  // raw storage bits of bias[n] (bf16: low 16 bits), converted where used
   float resid;
-  int past;
+  uint32_t past;  // unsigned: widening it for the cache index is no instruction on the loaded value (see below)
 };
 
 template <typename T>
@@ -211,14 +213,27 @@ __device__ __forceinline__ float bias_value(uint32_t bits) {
 // for it at once -- a whole HBM round trip before the weight stream is even issued.
 template <typename T>
 __device__ __forceinline__ EpiPre epi_prefetch(const Epi& e, int m, int n, bool valid) {
-  EpiPre p{0u, 0.f, 0};
+  EpiPre p{0u, 0.f, 0u};
   if (e.kind == EPI_ARGMAX) return p;  // uniform (kernel argument)
   const int nn = valid ? n : 0, mm = valid ? m : 0;
   if constexpr (sizeof(T) == 2) p.bias_bits = ((const unsigned short*)e.bias)[nn];
   else p.bias_bits = ((const uint32_t*)e.bias)[nn];
   if (e.kind == EPI_RESID) p.resid = e.resid[(size_t)mm * e.ldo + nn];
-  if (e.kind == EPI_QKV) p.past = e.past_dev ? e.past_dev[mm / e.seq] : e.past;
   return p;
+}
+
+// EPI_QKV's past_len of the lane's row, the third prefetched operand.  With one token (m = 0 in every lane) the
+// address is wave-uniform and past_dev[0] compiles to a scalar load through a pointer that is itself a kernel
+// argument: two scalar waits in a row ahead of the weight stream.  lane_zero() keeps it a vector load, in flight
+// with the bias load and the weight stream and waited for in the epilogue.  With several tokens the caller issues
+// it BEHIND its first weight loads: the epilogue is the only reader, so nothing waits for it earlier, and the
+// integer division of m / seq stays off the path to the first weight load.
+__device__ __forceinline__ void epi_prefetch_past(const Epi& e, int m, bool valid, EpiPre& p) {
+  if (e.kind != EPI_QKV) return;  // uniform (kernel argument)
+  const int mm = valid ? m : 0;
+  // (as a signed int the compiler hoists the sign extension of the 64-bit cache index up to the load and waits
+  // for it there, vmcnt(0): past_len is never negative)
+  p.past = e.past_dev ? (uint32_t)e.past_dev[mm / e.seq + lane_zero()] : (uint32_t)e.past;
 }
 
 // epi_store with the operands from epi_prefetch (same arithmetic, same roundings).
@@ -483,7 +498,7 @@ __device__ __forceinline__ void ln_rows_load(const LnArgs& ln, int M, int K, flo
 #pragma unroll
   for (int m = 0; m < MM; m++) {
     const float* xr = ln.x + ((size_t)min(m, M - 1) * ln.row_stride + ln.row_offset) * K;
-    c[m] = xr[0];
+    c[m] = xr[lane_zero()];  // a vector load beside the row's (xr[0] is a scalar load the wave waits for at once)
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const int k = threadIdx.x * 4 + i * 1024;
@@ -796,7 +811,7 @@ template <int MM>
 __device__ __forceinline__ void emb_rows_prefetch(const LnArgs& ln, int M, int K, int (&id)[MM], uint2 (&egb)[4][2],
                                                   uint2 (&gb)[4][2]) {
 #pragma unroll
-  for (int m = 0; m < MM; m++) id[m] = ln.ids[min(m, M - 1)];
+  for (int m = 0; m < MM; m++) id[m] = ln.ids[min(m, M - 1) + lane_zero()];  // vector loads (common.h lane_zero)
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const int k = min((int)threadIdx.x * 4 + i * 1024, K - 4);
@@ -883,6 +898,21 @@ __device__ __forceinline__ void gemv_rows_block(const bf16* __restrict__ W, cons
                                                 char* smem, unsigned* wait, unsigned target) {
   if constexpr (!SYNC) wait = nullptr;  // every poll / sc1 path below folds away
   constexpr bool LN = XM == X_LN;
+  {
+    // One empty asm statement that takes as SGPR inputs the argument fields the loads ahead of the weight stream
+    // build their addresses from: the compiler then reads them with the kernel's first group of argument loads,
+    // under its one wait, instead of sinking them into the blocks that use them (a second and third group, each
+    // with a wait of its own in front of the first weight load).  One statement: volatile asm statements keep
+    // their order, and several would split the argument loads into as many groups again.  Emits nothing.
+    const int bd = blockDim.x;
+    if constexpr (XM == X_PLAIN)  // no prologue: X and what the compiler reads early of the epilogue's fields instead
+      asm volatile("" ::"s"(W), "s"(X), "s"(M), "s"(N), "s"(K), "s"(bd), "s"(ep.kind), "s"(ep.bias), "s"(ep.resid),
+                   "s"(ep.ldo), "s"(ep.past_dev), "s"(ep.past), "s"(ep.slot), "s"(ep.keys), "s"(ep.logits));
+    else
+      asm volatile("" ::"s"(W), "s"(M), "s"(N), "s"(K), "s"(bd), "s"(ep.kind), "s"(ep.bias), "s"(ep.resid), "s"(ep.ldo),
+                   "s"(ep.past_dev), "s"(ep.past), "s"(ln.x), "s"(ln.row_stride), "s"(ln.row_offset), "s"(ln.gamma),
+                   "s"(ln.beta));
+  }
   BS_STAMP(0);
   float* scratch = reinterpret_cast<float*>(smem);                  // 64 floats
   bf16* xs = reinterpret_cast<bf16*>(smem + 256);                    // LN / PARTS: [M][K]
@@ -893,10 +923,14 @@ __device__ __forceinline__ void gemv_rows_block(const bf16* __restrict__ W, cons
   for (int r = 0; r < R; r++) wr[r] = W + (size_t)min(n0 + r, N - 1) * K;
   // lane j = r * MM + m stores (row r, token m) in the epilogue; its operands go out first
   const int er = lane / MM, em = lane % MM;
-  const EpiPre pre = epi_prefetch<bf16>(ep, em, n0 + er, lane < R * MM && em < M && n0 + er < N);
+  const bool evalid = lane < R * MM && em < M && n0 + er < N;
+  EpiPre pre = epi_prefetch<bf16>(ep, em, n0 + er, evalid);
+  if constexpr (MM == 1) epi_prefetch_past(ep, 0, evalid, pre);  // one token: row 0, no division
   // LN / PARTS: the activation loads are issued first, then the first U chunks of every weight
   // row, then the prologue math runs on the activations (their loads are the oldest, so waiting
-  // for them does not wait for the weights) while the weight stream is in flight
+  // for them does not wait for the weights) while the weight stream is in flight.  That is also what
+  // the compiler emits now: the LayerNorm shift is a vector load among the row loads (ln_rows_load), and
+  // the first wait behind the argument wait is the vmcnt in ln_rows_finish, after the weight issue.
   float4 xv[LN ? MM : 1][4];
   float xc[LN ? MM : 1];
   uint2 gb[4][2];
@@ -934,12 +968,16 @@ __device__ __forceinline__ void gemv_rows_block(const bf16* __restrict__ W, cons
 #pragma unroll
     for (int r = 0; r < R; r++) wv[u][r] = wload<!(FL & 1)>(wr[r] + k);
   }
+  if constexpr (MM > 1) epi_prefetch_past(ep, em, evalid, pre);  // m / seq: behind the weight issue
   const bf16* xg;
   int xstride;
   if constexpr (LN) {
     ln_rows_finish<MM>(ln, M, K, xv, xc, gb, xs, scratch);
     xg = xs; xstride = K;
   } else if constexpr (XM == X_EMB) {
+    // the embedding rows' addresses need the ids: keep the scheduler from moving those loads, and the wait for
+    // the ids with them, in front of the weight issue
+    __builtin_amdgcn_sched_barrier(0);
     emb_rows_finish<MM>(ln, M, K, eid, egb, gb, xs, scratch);
     xg = xs; xstride = K;
   } else if constexpr (XM == X_PARTS) {
@@ -2723,9 +2761,10 @@ void launch_linear(int is_bf16, const void* X, const void* W, int M, int N, int 
 // ------------------------------------------------------------------------------------
 // Decode (S == 1).  Block (head, row b, split) of WV waves; wave w of split sp takes the 64-position
 // chunks c = w + WV*(sp + nsplit*j).  16 lanes cover one 8-dim slice each of a key/value row, so
-// every load instruction reads 4 whole rows (coalesced); a chunk's K and V rows are requested
-// before q is staged (they do not depend on it), so the first chunk's HBM round trip overlaps the
-// q load.  Scores = ALiBi + q.k/sqrt(hd); online softmax across the wave's chunks; the wave
+// every load instruction reads 4 whole rows (coalesced).  past_len, the slope and q are requested first,
+// as vector loads; the first chunk's K and V rows right behind them (they depend on none of the three);
+// q is staged in LDS under a wait that leaves the chunk's loads in flight, and nothing is loaded between
+// that barrier and the chunk's math: one memory round trip before the first scores.  Scores = ALiBi + q.k/sqrt(hd); online softmax across the wave's chunks; the wave
 // partials merge through LDS.  nsplit == 1: the block writes ctx.  Otherwise it publishes a
 // (max, sum, context) partial write-through (sc1) and takes a ticket; the block drawing the last
 // ticket of its (row, head) merges all partials (sc1 loads, issued together) and writes ctx —
@@ -2767,18 +2806,29 @@ __device__ __forceinline__ void attn_decode_block(const AttnArgs& a, int head, i
       raw_load(vb + (size_t)pr * hd + doff, vr[it]);
     }
   };
-  // The first chunk is requested before past_len is known (clamped to the cache, not the context:
+  // q, the slope and past_len go out first, as three vector loads (their addresses are wave-uniform or nearly
+  // so; lane_zero() keeps the compiler from making the slope and past_len scalar loads, which it waits for one
+  // after the other and only after the chunk below has landed).  Every thread loads a q element (clamped), so
+  // no exec-masked branch stands in front of the chunk.
+  int past_v = a.past;
+  if (a.past_dev) past_v = a.past_dev[b + lane_zero()];
+  const float slope = a.slopes[head + lane_zero()];
+  const T qraw = ((const T*)a.q)[(size_t)b * a.hidden + head * hd + min((int)threadIdx.x, hd - 1)];
+  // The first chunk is requested behind them, before past_len is known (clamped to the cache, not the context:
   // positions past the context are masked to p = 0 below; the cache is zero-initialised and only
-  // ever holds finite values, so their V rows contribute 0 * finite) and before q is staged.
+  // ever holds finite values, so their V rows contribute 0 * finite) and before q is staged.  Unconditional:
+  // a wave whose first chunk lies past the cache re-reads the cache's last row and never uses it (c >= nch).
+  // Loads return in order, so staging q waits for the three loads above and leaves the chunk's in flight.
+  // (the scheduling barriers keep the instruction scheduler from moving the q load behind the chunk's loads,
+  // which it did, or anything of the staging in front of them)
+  __builtin_amdgcn_sched_barrier(0);
   int c = w + WV * sp;
-  if (c * CH < a.max_ctx) load_chunk(c, a.max_ctx - 1);
-  // q, the slope and past_len are independent of each other: all in flight with the first chunk
-  const float slope = a.slopes[head];
-  const float qreg = threadIdx.x < hd ? to_f32(((const T*)a.q)[(size_t)b * a.hidden + head * hd + threadIdx.x]) : 0.f;
-  const int past = a.past_dev ? a.past_dev[b] : a.past;
+  load_chunk(c, a.max_ctx - 1);
+  __builtin_amdgcn_sched_barrier(0);
+  if (threadIdx.x < hd) qs[threadIdx.x] = to_f32(qraw);  // hd <= 128 <= WV * 64
+  const int past = __builtin_amdgcn_readfirstlane(past_v);  // uniform again: the chunk loop's bound stays scalar
   const int nk = past + 1, nlast = nk - 1;
   const int nch = (nk + CH - 1) / CH;
-  if (threadIdx.x < hd) qs[threadIdx.x] = qreg;  // hd <= 128 <= WV * 64
   __syncthreads();
   float qv[8];
   {

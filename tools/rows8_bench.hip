@@ -31,7 +31,8 @@ __global__ __launch_bounds__(1024) void gemv_rows8_kernel(const bf16* __restrict
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int n0 = (blockIdx.x * nw + w) * R;
   const int er = lane >> 3, em = lane & 7;
-  const EpiPre pre = epi_prefetch<bf16>(ep, em, n0 + er, er < R && em < M && n0 + er < N);
+  EpiPre pre = epi_prefetch<bf16>(ep, em, n0 + er, er < R && em < M && n0 + er < N);
+  epi_prefetch_past(ep, em, er < R && em < M && n0 + er < N, pre);
   // activations by LDS-DMA: row m of the block's image at m * rb bytes; LN: gamma, beta after the rows
   const int rb = LN ? K * 4 : K * 2, npc = rb >> 10;  // bytes per row, 1-KB pieces per row
   {
