@@ -66,9 +66,12 @@ class BeamSearcher:
     [0, num_beams).  generate() prefills the prompt in row 0 with a top-k pass (k = 2W), forks row 0 to rows 1..W-1
     (bs_fork_kv), and then runs per step: plain forwards on the stages before the last, forward_topk(B = W, S = 1,
     k = 2W) on the last, the selection on the host, and copy_kv of assign_slots' pairs on every stage.
-    kv_copies counts the pairs copied (the first fork included) over the searcher's life."""
+    kv_copies counts the pairs copied (the first fork included) over the searcher's life.
+    prefix_attention: after the first fork the W rows declare the prompt's positions as row 0's (bs_set_row_prefix; every
+    hypothesis carries the prompt, so copy_kv keeps them equal) and the steps stream the prompt once per head."""
 
-    def __init__(self, stages, num_beams, length_penalty=1.0, eos=None, num_return=1, host_io=False):
+    def __init__(self, stages, num_beams, length_penalty=1.0, eos=None, num_return=1, host_io=False,
+                 prefix_attention=False):
         self.stages = list(stages)
         if not self.stages or not self.stages[0].is_first or not self.stages[-1].is_last:
             raise ValueError("a chain runs from a first stage to a last stage")
@@ -82,6 +85,7 @@ class BeamSearcher:
         self.eos = None if eos is None or eos < 0 else int(eos)
         self.max_ctx = min(st.max_ctx for st in self.stages)
         self.vocab = self.stages[-1].vocab
+        self.prefix_attention = bool(prefix_attention) and num_beams > 1
         self.kv_copies = 0
         self._buf = {}
         self._stream = None
@@ -134,6 +138,11 @@ class BeamSearcher:
                 st.copy_kv(pairs, npos, stream=stream)
         self.kv_copies += len(pairs)
 
+    def _declare(self, npos):
+        stream = None if self.host_io else (self._stream.cuda_stream if self._stream is not None else None)
+        for st in self.stages:
+            st.set_row_prefix(0, 0, npos, count=self.W, stream=stream)
+
     def generate(self, prompt, max_new):
         """Returns (sequences, scores, token_logprobs): the num_return best finished hypotheses, best first -- each
         one's generated tokens (an eos included), its score (sum of log-probs / length ** length_penalty) and the
@@ -146,6 +155,8 @@ class BeamSearcher:
         W, V, P = self.W, self.vocab, len(prompt)
         running = [_Hyp([], 0.0, [], 0)]  # in rank order
         finished = []                     # (score, tokens, logprobs), best first, at most W
+        if self.prefix_attention:
+            self._declare(0)  # the last sample's declaration: the prompt is prefilled at position 0
         ids, lps = self._run(prompt, 1, P, 0)
         for n in range(1, max_new + 1):  # n: tokens every candidate of this step holds
             # the 2W best candidates: by score, then by the lower flat index (rank of the parent, then token id)
@@ -180,6 +191,8 @@ class BeamSearcher:
             running = [_Hyp(running[w].tokens + [tok], score, running[w].logprobs + [lp], slots[i])
                        for i, (w, tok, lp, score) in enumerate(nxt)]
             self._copy(copies, P + n - 1, fork=(n == 1))
+            if self.prefix_attention and n == 1:
+                self._declare(P)
             feed = [0] * W
             for hyp in running:
                 feed[hyp.slot] = hyp.tokens[-1]

@@ -119,6 +119,23 @@ constexpr int kVerifyMaxTokens = 32;
 int attention_verify_split_stride(int n_head, int max_chunks);
 void launch_attention_verify(int is_bf16, const AttnArgs& a, hipStream_t s);
 
+// ---- Shared-prefix decode attention (bs_set_row_prefix; attn_prefix.hip) ----
+// One entry of the device table [max_batch]: the row's first npos cached positions hold the bits of row src_slot's
+// (npos == 0: no declaration).
+struct PrefixRow { int src_slot, npos; };
+constexpr int kPrefixMaxRows = 32;    // rows of a step on the shared route (two 16-row MFMA query tiles)
+constexpr int kPrefixMaxSplits = 16;
+// Splits of the prefix per head: a function of the stage alone, so a captured launch stays valid for every npos.
+int attention_prefix_splits(int n_head, int max_ctx);
+// table[slot .. slot + count) = {src_slot, npos}, stream ordered, by kernel arguments.
+void launch_prefix_table(PrefixRow* table, int slot, int count, int src_slot, int npos, hipStream_t s);
+// S == 1, bf16, head_dim <= 128, 2 <= a.B <= kPrefixMaxRows, every row of the call holding table[a.slot]'s
+// declaration with npos > 0 and past_b >= npos (the host checks): the prefix of row src_slot once per head over
+// a.max_chunks = attention_prefix_splits splits -> a.part_acc / a.part_ml, the prefix partials [kPrefixMaxRows]
+// [n_head][splits][head_dim] and [..][2]; then each row's own positions [npos, past_b] and the merge -> a.ctx_out.
+// Two launches on a static grid; rows' lengths from a.past_dev (non-null).
+void launch_attention_prefix(const AttnArgs& a, const PrefixRow* table, hipStream_t s);
+
 // ---- Int8 KV cache (bf16 stages with BS_FLAG_INT8_KV; kv_int8.hip) ----
 // The fp32 scales beside the int8 codes of one layer ([max_batch][heads][max_ctx], K and V), and the bf16 staging
 // buffers the QKV epilogue writes a call's new K / V rows to ([B][heads][lmax][hd], slot 0).

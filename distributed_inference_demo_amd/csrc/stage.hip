@@ -11,7 +11,7 @@
 //   errors and tracing; Carver (one device allocation cut into aligned pieces); bs_stage and the allocations it owns
 //   validate, bs_stage_weight_count (the weight table is stage_weights.h), checkpoint lookup
 //   init_stage: weight arena + binding, the three weight sources, head screening, KV cache, workspace
-//   bs_stage_info, bs_read_weights, bs_read_kv, bs_reset_kv, bs_fork_kv, bs_copy_kv
+//   bs_stage_info, bs_read_weights, bs_read_kv, bs_reset_kv, bs_set_row_prefix, bs_fork_kv, bs_copy_kv
 //   profiling, bs_stream_delay, the HBM and MFMA probes
 //   the forward: linear / linear_ln, Tail (which tail a pass ends in, decided once), enqueue_forward
 //   head slices, sampling setters, the per-row sampler and verify-draw buffers, the graph cache
@@ -105,8 +105,10 @@ struct GraphKey {
   int k = 0;  // TAIL_TOPK_LOGPROBS: candidates per row, and where the log-probs and the lse go (out = the ids)
   const void* logprobs = nullptr;
   const void* lse = nullptr;
+  int prefix = 0;  // the step's attention takes the shared-prefix route (prefix_route); (src_slot, npos) are not part
+                   // of the key: the kernels read them from the device table
   bool operator==(const GraphKey& o) const {
-    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && tail == o.tail && in == o.in &&
+    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && tail == o.tail && prefix == o.prefix && in == o.in &&
            out == o.out && logits == o.logits && st == o.st && k == o.k && logprobs == o.logprobs && lse == o.lse;
   }
 };
@@ -300,6 +302,15 @@ struct bs_stage {
   int* tk_ids = nullptr;                // [max_batch][kTopkMaxK]
   float* tk_lp = nullptr;               // [max_batch][kTopkMaxK]
   float* tk_lse = nullptr;              // [max_batch]
+  // shared-prefix decode attention (attn_prefix.hip): the device table of the rows' declarations and the prefix
+  // partials of one step, one allocation made by the first bs_set_row_prefix (px_table null: never called); px_host
+  // mirrors the table for routing and for bs_forward's past_len check
+  PrefixRow* px_table = nullptr;       // [max_batch]
+  float* px_acc = nullptr;             // [kPrefixMaxRows][n_head][px_splits][hd]
+  float* px_ml = nullptr;              // [kPrefixMaxRows][n_head][px_splits][2]
+  int px_splits = 0;                   // attention_prefix_splits
+  std::vector<PrefixRow> px_host;      // [max_batch]
+  int px_active = 0;                   // rows that hold a declaration
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -875,7 +886,55 @@ extern "C" int bs_reset_kv(bs_stage* s, int32_t slot) {
       if (slot < 0) HIP_TRY(hipMemsetAsync(sc, 0, s->kv_sc_half * 4, s->own));
       else HIP_TRY(hipMemsetAsync(sc + (size_t)slot * srow, 0, srow * 4, s->own));
     }
+  if (s->px_active) {  // the row's prefix declaration goes with its content
+    const int r0 = slot < 0 ? 0 : slot, n = slot < 0 ? s->d.max_batch : 1;
+    launch_prefix_table(s->px_table, r0, n, 0, 0, s->own);
+    for (int i = r0; i < r0 + n; i++) {
+      if (s->px_host[i].npos) s->px_active--;
+      s->px_host[i] = PrefixRow{0, 0};
+    }
+  }
   HIP_TRY(hipStreamSynchronize(s->own));
+  return BS_OK;
+}
+
+// Shared-prefix declarations (attn_prefix.hip).  The first call makes the table (zeroed: no row declares anything) and
+// the partials workspace; every call is one small launch on the caller's stream and a host mirror update.  The
+// captured graphs stay: the route is a bit of their key and (src_slot, npos) are read on the device.
+extern "C" int bs_set_row_prefix(bs_stage* s, int32_t slot, int32_t count, int32_t src_slot, int32_t npos, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (!s->bf16) return fail(BS_ERR_UNSUPPORTED, "bs_set_row_prefix needs a bf16 stage");
+  if (s->kv8) return fail(BS_ERR_UNSUPPORTED, "bs_set_row_prefix on an int8 KV cache is not supported");
+  if (s->hd > 128) return fail(BS_ERR_UNSUPPORTED, "bs_set_row_prefix needs head_dim <= 128");
+  const int mb = s->d.max_batch;
+  if (count <= 0 || slot < 0 || slot > mb - count) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (src_slot < 0 || src_slot >= mb) return fail(BS_ERR_INVALID, "src_slot outside max_batch");
+  if (npos < 0 || npos > s->d.max_ctx) return fail(BS_ERR_INVALID, "npos outside [0, max_ctx]");
+  if (!s->px_table && !npos) return BS_OK;  // nothing was ever declared
+  HIP_TRY(hipSetDevice(s->d.device));
+  if (!s->px_table) {
+    const int ns = attention_prefix_splits(s->d.n_head, s->d.max_ctx);
+    const size_t recs = (size_t)kPrefixMaxRows * s->d.n_head * ns;
+    PrefixRow* table = nullptr;
+    float *acc = nullptr, *ml = nullptr;
+    Carver c;
+    c.piece(&table, (size_t)mb * sizeof(PrefixRow));
+    c.piece(&acc, recs * s->hd * 4);
+    c.piece(&ml, recs * 2 * 4);
+    const int ar = c.alloc(s->own);
+    if (ar == Carver::NO_MEMORY) return fail(BS_ERR_OOM, "prefix attention allocation failed (" + std::to_string(c.total) + " B)");
+    if (ar == Carver::NOT_ZEROED) return fail(BS_ERR_DEVICE, "prefix table memset");
+    s->owned.push_back({c.base, c.total});
+    s->px_table = table; s->px_acc = acc; s->px_ml = ml; s->px_splits = ns;
+    s->px_host.assign(mb, PrefixRow{0, 0});
+  }
+  launch_prefix_table(s->px_table, slot, count, npos ? src_slot : 0, npos, stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("prefix table: ") + hipGetErrorString(err));
+  for (int i = slot; i < slot + count; i++) {
+    s->px_active += (npos ? 1 : 0) - (s->px_host[i].npos ? 1 : 0);
+    s->px_host[i] = PrefixRow{npos ? src_slot : 0, npos};
+  }
   return BS_OK;
 }
 
@@ -1231,6 +1290,21 @@ static bool rows_guided(const bs_stage* s, int slot, int B) {
   return false;
 }
 
+// Does this step's attention take the shared-prefix route (attn_prefix.hip)?  A plain decode step of 2 .. 32 rows that
+// all hold the same declaration, each row at or beyond the shared positions.
+static bool prefix_route(const bs_stage* s, const bs_step* step, const std::vector<int>& pasts) {
+  const int B = step->batch;
+  if (!s->px_active || step->seq != 1 || (step->flags & BS_STEP_VERIFY) || B < 2 || B > kPrefixMaxRows || s->L <= 0)
+    return false;
+  const PrefixRow p0 = s->px_host[step->slot];
+  if (p0.npos <= 0) return false;
+  for (int b = 0; b < B; b++) {
+    const PrefixRow& p = s->px_host[step->slot + b];
+    if (p.src_slot != p0.src_slot || p.npos != p0.npos || pasts[b] < p0.npos) return false;
+  }
+  return true;
+}
+
 // Which tail this pass ends in (scoring: a bs_forward_score pass).  forward_impl has checked the step against the stage.
 static Tail plan_tail(const bs_stage* s, const bs_step* step, bool scoring, bool topk = false) {
   const int B = step->batch, M = B * step->seq, V = s->d.vocab;
@@ -1296,11 +1370,11 @@ static int tail_copy_out(const Tail& t, const bs_step* step, const int* tok, voi
 
 // Enqueue one forward on `st`.  The kernels read each row's past_len from past_dev (device [B],
 // written ahead of the forward or of the graph replay); `pasts` is the host copy (profiling bytes).
-// tail: what forward_impl planned; sc: what a TAIL_SCORE reads and writes (bs_forward_score); tk: what a
+// shared: the attention takes the shared-prefix route (prefix_route).  tail: what forward_impl planned; sc: what a TAIL_SCORE reads and writes (bs_forward_score); tk: what a
 // TAIL_TOPK_LOGPROBS writes (bs_forward_topk).
 static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, const void* in, void* out, float* logits,
                            hipStream_t st, const int* past_dev, const std::vector<int>& pasts,
-                           const ScoreIO* sc = nullptr, const TopkIO* tk = nullptr) {
+                           const ScoreIO* sc = nullptr, const TopkIO* tk = nullptr, bool shared = false) {
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot, past = pasts[0];
   double ctx_sum = 0.0;
@@ -1374,11 +1448,18 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
     // a split decode context merges in the dense GEMV's prologue when that kernel can take it
     const int nsplit = S == 1 ? attention_decode_splits(B, nh, s->max_chunks) : 1;
     const WMat dense = wmat(w, T_DENSE_W);
-    a.defer_merge = s->bf16 && nsplit > 1 && wmat_parts_supported(dense, M, h, hd, nsplit);
+    a.defer_merge = !shared && s->bf16 && nsplit > 1 && wmat_parts_supported(dense, M, h, hd, nsplit);
     // a = x + dense(ctx)
     Epi e2{};
     e2.kind = EPI_RESID; e2.bias = w.t[T_DENSE_B]; e2.out_f32 = s->attn; e2.resid = cur; e2.ldo = h;
-    if (verify) {
+    if (shared) {
+      // the common prefix once per head, then each row's own positions and the merge (attn_prefix.hip)
+      const int np = s->px_host[slot].npos;
+      ProfScope p(s, st, 3, ((double)np + (ctx_sum - (double)B * np)) * nh * hd * 2 * s->esz);
+      AttnArgs ap = a;
+      ap.part_acc = s->px_acc; ap.part_ml = s->px_ml; ap.max_chunks = s->px_splits;
+      launch_attention_prefix(ap, s->px_table, st);
+    } else if (verify) {
       // short-query split-context attention on a static grid (attn_verify.hip): every row's length from past_dev
       ProfScope p(s, st, 3, ctx_sum * nh * hd * 2 * s->esz);
       AttnArgs av = a;
@@ -2140,6 +2221,9 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     if (pasts[b] < 0 || pasts[b] + S > d.max_ctx) return fail(BS_ERR_INVALID, "past_len + seq exceeds max_ctx");
   }
   if (M > d.max_tokens) return fail(BS_ERR_INVALID, "batch*seq exceeds max_tokens");
+  for (int b = 0; s->px_active && b < B; b++)
+    if (pasts[b] < s->px_host[slot + b].npos)
+      return fail(BS_ERR_INVALID, "past_len below the row's shared prefix (bs_set_row_prefix)");
   if (s->kv8 && S > 1 && s->L > 0) {  // every row's past and new positions side by side in the bf16 staging
     const size_t need = (size_t)B * (*std::max_element(pasts.begin(), pasts.end()) + S);
     if (need > s->kv_stage_cap)
@@ -2214,14 +2298,16 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   s->past_next_valid = false;  // until this forward is enqueued
   const bool graph = (S == 1 || verify) && !host_io && s->prof.cls == 0 && s->graphs_on && !sc;  // scoring is always eager
   hipGraphExec_t exec = nullptr;
+  const bool shared = prefix_route(s, step, pasts);
   GraphKey key{B, S, slot, step->flags, tail.kind, in, out, logits, st};
+  key.prefix = shared ? 1 : 0;
   if (tk) { key.out = tk->ids; key.logits = tk->logits; key.k = tk->k; key.logprobs = tk->logprobs; key.lse = tk->lse; }
   if (graph && !(exec = find_graph(s, key))) {
     hipGraph_t gr = nullptr;
     BS_TRACE("hipStreamBeginCapture");
     HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
     BS_TRACE("enqueue_forward (capturing)");
-    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, nullptr, tk);
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, nullptr, tk, shared);
     BS_TRACE("hipStreamEndCapture");
     hipError_t ce = hipStreamEndCapture(st, &gr);
     if (rc != BS_OK) { if (gr) hipGraphDestroy(gr); return rc; }
@@ -2242,7 +2328,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     HIP_TRY(hipGraphLaunch(exec, st));
   } else {
     BS_TRACE("enqueue_forward (eager)");
-    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, sc, tk);
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, sc, tk, shared);
     if (rc != BS_OK) return rc;
   }
   BS_TRACE("hipGetLastError");

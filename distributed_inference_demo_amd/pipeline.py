@@ -139,6 +139,14 @@ class StageExecutor:
             return
         self._run(lambda h: self.stage.fork_kv(src, dst, npos, count=count, stream=h), ())
 
+    def set_row_prefix(self, slot, src_slot, npos):
+        """Stage.set_row_prefix of KV row `slot` (npos 0 clears), ordered like forward."""
+        sh = self._sh if self._sh is not None else torch.cuda.current_stream().cuda_stream
+        if sh:
+            self.stage.set_row_prefix(slot, src_slot, npos, stream=sh)
+            return
+        self._run(lambda h: self.stage.set_row_prefix(slot, src_slot, npos, stream=h), ())
+
     def head_norm(self, hidden, batch, seq, xn):
         sh = torch.cuda.current_stream().cuda_stream
         if sh:
@@ -357,6 +365,11 @@ class Pipeline:
         every rank inside its own stage (bs_fork_kv), ordered with the rank's forwards on its current stream.  No
         communication; every rank calls this in the same order as every other rank."""
         self.ex.fork_kv(src_slot, j * self.mb + r, npos)
+
+    def set_row_prefix(self, j, r, src_slot, npos):
+        """Row r of micro-batch j declares its first npos cached positions as KV row `src_slot`'s (after fork_row; npos 0
+        clears), on every rank's stage (bs_set_row_prefix), ordered like fork_row.  No communication."""
+        self.ex.set_row_prefix(j * self.mb + r, src_slot, npos)
 
     def prefill_row(self, j, r, ids, n, past=0, slot=None):
         """One pipeline pass of row r of micro-batch j alone: its n prompt tokens at positions past..past+n-1 of KV

@@ -122,7 +122,7 @@ EXPORTS = [
     "bs_build_id", "bs_hbm_probe", "bs_mfma_probe", "bs_init_stage_file", "bs_weights_file_probe",
     "bs_set_graphs", "bs_binary_classify", "bs_set_head_screen", "bs_read_head_screen",
     "bs_forward_score", "bs_set_row_sampler", "bs_sample_logits", "bs_read_row_draw",
-    "bs_read_verify_draw", "bs_fork_kv", "bs_copy_kv", "bs_forward_topk",
+    "bs_read_verify_draw", "bs_fork_kv", "bs_copy_kv", "bs_forward_topk", "bs_set_row_prefix",
     "bs_set_row_processor", "bs_note_tokens", "bs_process_logits", "bs_read_row_tokens",
     "bs_load_guide", "bs_unload_guide", "bs_set_row_guide", "bs_advance_row_guide", "bs_guide_logits",
     "bs_read_row_guide",
@@ -157,6 +157,7 @@ def lib():
         L.bs_read_kv.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bs_fork_kv.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bs_copy_kv.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, i32, vp]
+        L.bs_set_row_prefix.argtypes = [vp, i32, i32, i32, i32, vp]
         L.bs_forward_topk.argtypes = [vp, ctypes.POINTER(Step), vp, i32, vp, vp, vp, vp, vp]
         L.bs_release.argtypes = [vp]
         L.bs_release.restype = None
@@ -686,6 +687,12 @@ class Stage:
         _check(lib().bs_copy_kv(self._h, src, dst, n, int(npos), stream))
         for _, b in pairs:
             self.past[b] = int(npos)
+
+    def set_row_prefix(self, slot, src_slot, npos, count=1, stream=None):
+        """bs_set_row_prefix: rows [slot, slot + count) declare that their first npos cached positions hold the bits
+        of row src_slot's (fork_kv / copy_kv made them so); npos 0 clears.  Decode steps of 2 .. 32 rows that all
+        hold the same declaration then read that prefix once per head.  Stream ordered like forward()."""
+        _check(lib().bs_set_row_prefix(self._h, int(slot), int(count), int(src_slot), int(npos), stream))
 
     def read_kv(self, layer, slot, pos0, npos):
         """KV row `slot` of local layer `layer`, positions [pos0, pos0+npos): fp32 [2 (K, V)][n_head][npos][hd]."""

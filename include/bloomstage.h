@@ -14,6 +14,7 @@
  *   bs_reset_kv        <- (none: the reference has no KV cache; new sample == new slot)
  *   bs_fork_kv         <- (none: no KV cache, so no shared prompt prefix to reuse)
  *   bs_copy_kv         <- (none: no KV cache, so no hypotheses' rows to reorder)
+ *   bs_set_row_prefix  <- (none: no KV cache, so no shared prefix to read once)
  *   bs_forward_score   <- (none: the reference has no scoring task)
  *   bs_forward_topk    <- (none: the reference's tail returns one token, decoding.cpp:24-66, never ranked candidates)
  *   bs_last_error      <- (none: the reference throws C++ exceptions across JNI,
@@ -562,7 +563,8 @@ int bs_set_head_screen(bs_stage *stage, int32_t on);
  * for vocab/16 entries).  hilo, lstar and list may be NULL.  Synchronizes the device. */
 int bs_read_head_screen(bs_stage *stage, int32_t row, float *hilo, float *lstar, int32_t *list, int32_t *count);
 
-/* Forget the cached positions of one KV row (slot), or of all rows when slot < 0. */
+/* Forget the cached positions of one KV row (slot), or of all rows when slot < 0, and the rows' shared-prefix
+ * declarations (bs_set_row_prefix). */
 int bs_reset_kv(bs_stage *stage, int32_t slot);
 /* Read back KV row `slot` of the stage's local layer `layer`, positions [pos0, pos0 + npos), as fp32
  * out[2 (K, V)][n_head][npos][head_dim].  Synchronizes the stage's own stream; the caller orders any
@@ -598,6 +600,26 @@ int bs_fork_kv(bs_stage *stage, int32_t src_slot, int32_t dst_slot, int32_t coun
  *   appears twice, a destination that is also a source (so the launches have no ordering hazard among themselves). */
 int bs_copy_kv(bs_stage *stage, const int32_t *src_slots, const int32_t *dst_slots, int32_t count, int32_t npos,
                void *stream);
+/* Shared-prefix decode attention: rows [slot, slot + count) declare that their first npos
+ * cached positions hold the same bits as row src_slot's first npos positions -- bs_fork_kv or bs_copy_kv made them
+ * so; src_slot may be one of the rows.  npos == 0 clears the declaration.  Stream-ordered on `stream` (NULL = the
+ * stage's own) like a forward, no synchronisation, captured graphs stay.  The first call allocates the device table of
+ * declarations and the partials workspace (counted under workspace_bytes); a stage that never calls it is unchanged.
+ *   A bs_forward / bs_forward_topk step takes the shared route when seq == 1 without BS_STEP_VERIFY, 2 <= batch <= 32,
+ *   every row of the call holds the same (src_slot, npos) with npos > 0, and every past_len >= npos.  Then the
+ *   attention reads positions [0, npos) of src_slot ONCE per head for all rows of the call (matrix cores), and each
+ *   row's own positions [npos, past_len] in a second launch that also merges; the result is bit-identical from run to
+ *   run and between graph replay and eager launches, and within bf16 rounding of the plain route's.  Every other
+ *   step runs exactly as without declarations, bit for bit.
+ *   Contract: the shared route never reads a row's own first npos positions, only src_slot's; the caller keeps
+ *   src_slot's first npos positions untouched while rows reference it (bs_copy_kv of at least npos positions of rows
+ *   that all begin with them rewrites the same bits and is allowed).  bs_reset_kv clears the declaration of the rows it
+ *   resets.  A captured step follows a later call of the same shape without recapture: the kernels read (src_slot,
+ *   npos) from the device table.
+ *   BS_ERR_UNSUPPORTED: an fp32 stage, a BS_FLAG_INT8_KV stage, head_dim > 128.  BS_ERR_INVALID: a slot range or src_slot
+ *   outside max_batch, count <= 0, npos outside [0, max_ctx]; and from bs_forward, bs_forward_score and bs_forward_topk
+ *   when a row of the call holds a declaration and its past_len < npos. */
+int bs_set_row_prefix(bs_stage *stage, int32_t slot, int32_t count, int32_t src_slot, int32_t npos, void *stream);
 
 void bs_release(bs_stage *stage);
 
