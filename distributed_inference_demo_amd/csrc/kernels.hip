@@ -3778,8 +3778,166 @@ static void gemv_mx4_launch(const uint8_t* Q, const uint8_t* SC, const bf16* X, 
 // matrices) -- the 8-row instance re-reads 8 activation rows per weight row, from LDS on narrow models (+19..30 %
 // at h 1024 / 1536) but from L2 on wide ones (-14 % at h 2560 / 4096); above 8 rows never (passes of 8 rows lose at
 // every width, 1.3x at 16 rows to 3.7x at 32).
+// Since gemv_mx4_tiles (below) this rule is reached at 5..8 rows only by K % 128 != 0: on every K the tile GEMV takes
+// it is ahead of both routes (profiles/mxfp4_tiles_sweep.txt, M = 8: bloom-1b1 QKV 5.3 us against 7.7 for the 8-row
+// instance and 14.3 for dequant + bf16; 560m dense 3.7 / 4.8 / 6.4; 7b1 fc1 15.0 / 72.0 / 56.5; M = 32: 1b1 QKV 8.2
+// against 16.3 for dequant + bf16, 7b1 fc2 31.5 against 66.7).
 static bool linear_mx4_gemv(int M, int N, int K) {
   return M >= 1 && K % 32 == 0 && (M <= 4 || (M <= 8 && std::min(N, K) <= 2048));
+}
+
+// ------------------------------------------------------------------------------------
+// gemv_mx4_tiles: batched decode on MXFP4 weights, 4 < M <= 16 MT rows, K % 128 == 0.  The records go from global
+// memory straight into MFMA A fragments, no LDS stage and no dequant pass.  A block owns T 16-row weight tiles, its
+// 8 waves (times gridDim.y K splits) split the row's K / 128 groups of four blocks as evenly as they divide (parts
+// of unequal length where they do not: K = 1536 is 12 groups, 2560 is 20).  Per group q, lane (r = lane & 15,
+// g = lane >> 4) loads the whole 16-B record of block b = 4 q + g of weight row n0 + 16 t + r (one non-temporal
+// dwordx4; the four lanes g of a row read 64 contiguous bytes) and its scale byte.  The record's dword d is the A
+// fragment of k-step d: four v_cvt_scalef32_pk_bf16_fp4 (the block scale 2^(E - 127) is the operand) turn it into a
+// bf16x8 of the weights k = 32 b + 8 ((d + rot) & 3) + i, i = 0..7, rot = (b >> 2) & 3 = q & 3 (the record's
+// rotation, wave-uniform here).  The B fragment of lane (m = r, g) is the matching 16 bytes X[m][k .. k + 8) from
+// L2; rows past M load nothing.  A and B give the 32 slots of a k-step the same k, so every dot product is complete
+// after the group's four v_mfma_f32_16x16x32_bf16 per (tile, m-tile).  One B fragment serves all T tiles and each
+// weight is converted once for up to 32 rows.  The next group's records, scales and B fragments are in registers
+// while this one is computed.  Partial last tiles clamp their rows (tiles_epilogue skips their stores).
+// ------------------------------------------------------------------------------------
+template <int T, int MT>
+__global__ __launch_bounds__(512)
+void gemv_mx4_tiles_kernel(const uint8_t* __restrict__ Q, const uint8_t* __restrict__ SC, const bf16* __restrict__ X,
+                           int M, int N, int K, Epi ep) {
+  constexpr int WAVES = 8;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* red = reinterpret_cast<float*>(smem);  // [WAVES][T * 16][MT * 16 + 1]
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * (T * 16);
+  const int nb = K >> 5, ng = K >> 7;
+  const int nparts = gridDim.y * WAVES, part = blockIdx.y * WAVES + w;
+  const int q0 = ng * part / nparts, q1 = ng * (part + 1) / nparts;  // this wave's groups
+  const uint8_t* qp[T];
+  const uint8_t* sp[T];
+#pragma unroll
+  for (int t = 0; t < T; t++) {
+    const size_t row = (size_t)min(n0 + t * 16 + r, N - 1);
+    qp[t] = Q + (row * nb + g) * 16;
+    sp[t] = SC + row * nb + g;
+  }
+  const bf16* xp[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; mt++) xp[mt] = X + (size_t)min(mt * 16 + r, M - 1) * K + 32 * g;
+  auto load = [&](int q, u32x4v (&a)[T], uint32_t (&e)[T], bf16x8 (&b)[MT][4]) {
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+      a[t] = __builtin_nontemporal_load(reinterpret_cast<const u32x4v*>(qp[t] + (size_t)q * 64));
+      e[t] = sp[t][4 * q];
+    }
+    const int rot = q & 3;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int d = 0; d < 4; d++)
+        b[mt][d] = mt * 16 + r < M ? *reinterpret_cast<const bf16x8*>(xp[mt] + (size_t)q * 128 + 8 * ((d + rot) & 3))
+                                   : (bf16x8){};
+  };
+  f32x4 acc[T][MT];
+#pragma unroll
+  for (int t = 0; t < T; t++)
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++) acc[t][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  auto compute = [&](const u32x4v (&a)[T], const uint32_t (&e)[T], const bf16x8 (&b)[MT][4]) {
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+      const float scf = __uint_as_float(e[t] << 23);  // 2^(E - 127)
+#pragma unroll
+      for (int d = 0; d < 4; d++) {
+        const uint32_t c = a[t][d];
+        const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scf, 0);
+        const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scf, 1);
+        const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scf, 2);
+        const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scf, 3);
+        const bf16x8 af = {p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++) acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b[mt][d], acc[t][mt], 0, 0, 0);
+      }
+    }
+  };
+  if (q0 < q1) {
+    u32x4v a[2][T];
+    uint32_t e[2][T];
+    bf16x8 b[2][MT][4];
+    load(q0, a[0], e[0], b[0]);
+    for (int q = q0; q < q1; q += 2) {  // wave-uniform branches
+      if (q + 1 < q1) load(q + 1, a[1], e[1], b[1]);
+      compute(a[0], e[0], b[0]);
+      if (q + 1 < q1) {
+        if (q + 2 < q1) load(q + 2, a[0], e[0], b[0]);
+        compute(a[1], e[1], b[1]);
+      }
+    }
+  }
+  tiles_epilogue<T, MT, WAVES>(acc, red, M, N, n0, ep);
+}
+
+template <int T, int MT>
+static void gemv_mx4_tiles_launch(const uint8_t* Q, const uint8_t* SC, const bf16* X, int M, int N, int K, int KS,
+                                  const Epi& ep, hipStream_t s) {
+  const size_t shm = sizeof(float) * 8 * (T * 16) * (MT * 16 + 1);
+  const int blocks = (N + T * 16 - 1) / (T * 16);
+  gemv_mx4_tiles_kernel<T, MT><<<dim3(blocks, KS), 512, shm, s>>>(Q, SC, X, M, N, K, ep);
+}
+
+// (T, KS) of gemv_mx4_tiles for M <= 16 and M <= 32.  Shapes outside the table: one tile per block (two from
+// N >= 8192), K split in two until the grid has 256 blocks while every wave keeps at least two groups.
+// The BLOOM shapes take the fastest arm of `tools/tiles_bench mx4` (profiles/mxfp4_tiles_sweep.txt; M = 16 and 32).
+// Two m-tiles run at most two weight tiles per block: only those instances are built.
+struct Mx4TileCfg { int N, K, T1, KS1, T2, KS2; };
+static const Mx4TileCfg kMx4TileTable[] = {
+  {3072, 1024, 1, 1, 1, 1},  {1024, 1024, 1, 1, 1, 1},  {4096, 1024, 1, 1, 1, 1},  {1024, 4096, 1, 3, 1, 4},
+  {4608, 1536, 2, 1, 2, 1},  {1536, 1536, 1, 1, 1, 1},  {6144, 1536, 2, 1, 2, 1},  {1536, 6144, 2, 4, 2, 4},
+  {7680, 2560, 2, 1, 2, 1},  {2560, 2560, 1, 1, 1, 1},  {10240, 2560, 3, 1, 2, 1}, {2560, 10240, 2, 3, 2, 3},
+  {12288, 4096, 3, 1, 2, 1}, {4096, 4096, 1, 1, 2, 2},  {16384, 4096, 4, 1, 2, 1}, {4096, 16384, 4, 4, 2, 2},
+};
+
+// BS_MX4_TILES=0 (read once) sends every shape to the routes of linear_mx4_gemv / the dequant pass, for A/B runs.
+static bool mx4_tiles_takes(int M, int N, int K) {
+  static const bool on = [] {
+    const char* e = getenv("BS_MX4_TILES");
+    return !e || atoi(e) != 0;
+  }();
+  return on && M > 4 && M <= 32 && K % 128 == 0;
+}
+
+static void gemv_mx4_tiles_dispatch(const uint8_t* Q, const uint8_t* SC, const bf16* X, int M, int N, int K,
+                                    const Epi& ep, hipStream_t s, int T = 0, int KS = 0) {
+  const bool two = M > 16;
+  const int ng = K / 128;
+  if (T == 0) {
+    for (const Mx4TileCfg& c : kMx4TileTable)
+      if (c.N == N && c.K == K) { T = two ? c.T2 : c.T1; KS = two ? c.KS2 : c.KS1; }
+  }
+  if (T == 0) {
+    T = N >= 8192 ? 2 : 1;
+    KS = 1;
+    const int blocks = (N + T * 16 - 1) / (T * 16);
+    while (blocks * KS < 256 && ng / (KS * 2 * 8) >= 2) KS *= 2;
+  }
+  if (two) T = std::min(T, 2);
+  const int blocks = (N + T * 16 - 1) / (T * 16);
+  if (KS > 1 && !(ep.sk_ws && ep.sk_tickets && blocks <= ep.sk_ntickets && (size_t)KS * M * N <= ep.sk_cap)) KS = 1;
+  auto go = [&](auto tc) {
+    constexpr int TT = decltype(tc)::value;
+    if constexpr (TT <= 2) {  // two m-tiles: at most two weight tiles per block
+      if (two) {
+        gemv_mx4_tiles_launch<TT, 2>(Q, SC, X, M, N, K, KS, ep, s);
+        return;
+      }
+    }
+    gemv_mx4_tiles_launch<TT, 1>(Q, SC, X, M, N, K, KS, ep, s);
+  };
+  if (T >= 4) go(EpiKindC<4>{});
+  else if (T == 3) go(EpiKindC<3>{});
+  else if (T == 2) go(EpiKindC<2>{});
+  else go(EpiKindC<1>{});
 }
 
 // ------------------------------------------------------------------------------------
@@ -3815,7 +3973,7 @@ static void gemv_wq_launch(const WMat& w, const bf16* X, const LnArgs& ln, const
 }
 
 bool wmat_streams(int is_bf16, const WMat& w, int M, int N, int K) {
-  if (w.blk_scale) return linear_mx4_gemv(M, N, K);
+  if (w.blk_scale) return mx4_tiles_takes(M, N, K) || linear_mx4_gemv(M, N, K);
   return is_bf16 && M <= 32;  // int8: the tile GEMV or the int8 GEMV (a K % 32 != 0 matrix is dequantised all the same)
 }
 
@@ -3848,6 +4006,11 @@ void launch_wmat(int is_bf16, const void* X, const WMat& w, void* w_scratch, int
   // int8, batched decode (4 < M <= 32): the int8 gemv_ldsw4 / tile GEMV converts in registers (no dequant pass);
   // at M = 8 it reads the weights once where gemv_q8 re-reads activations per row (bloom-7b1 int8 B=8)
   if (w.row_scale && M > 4 && M <= 32 && gemv_tiles_dispatch<int8_t>(x, (const int8_t*)w.w, M, N, K, e, s)) return;
+  // MXFP4, batched decode: the fp4 tile GEMV converts the records in registers (no dequant pass either)
+  if (w.blk_scale && mx4_tiles_takes(M, N, K)) {
+    gemv_mx4_tiles_dispatch((const uint8_t*)w.w, w.blk_scale, x, M, N, K, e, s);
+    return;
+  }
   if (w.blk_scale ? linear_mx4_gemv(M, N, K) : linear_q8_gemv(M, K)) {
     gemv_wq_launch<false, false>(w, x, LnArgs{}, AttnParts{}, M, N, K, e, s);
     return;
