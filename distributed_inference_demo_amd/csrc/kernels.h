@@ -136,6 +136,31 @@ void launch_prefix_table(PrefixRow* table, int slot, int count, int src_slot, in
 // Two launches on a static grid; rows' lengths from a.past_dev (non-null).
 void launch_attention_prefix(const AttnArgs& a, const PrefixRow* table, hipStream_t s);
 
+// ---- Ragged prefill attention (bs_forward_ragged; attn_ragged.hip) ----
+// One row of a ragged pass: its KV row, its first token among the pass's T packed tokens, its new tokens and the
+// positions its KV row already holds.  One work item: a 64-query tile of a row.
+struct RaggedRow { int slot, t0, S, past; };
+struct RaggedWork { int row, qtile; };
+struct RaggedArgs {
+  const void* q;         // bf16 [T][hidden]
+  void* k_cache;         // bf16 layer base [max_batch][heads][max_ctx][hd]
+  void* v_cache;
+  const void* k_stage;   // bf16 [heads][T][hd]: the pass's new K / V (the QKV epilogue's output)
+  const void* v_stage;
+  void* ctx_out;         // bf16 [T][hidden]
+  const float* slopes;   // [n_head]
+  const RaggedRow* rows; // device [B]
+  const RaggedWork* work;  // device [nwork]
+  int nwork, T, n_head, head_dim, max_ctx, hidden;
+  float inv_norm;
+};
+// Attention of every (row, head, query tile) over the row's cached past and the pass's own positions, and the copy
+// of the new K / V from staging to cache[slot][head][past, past + S) by the blocks of query tile 0.  head_dim % 8 == 0
+// and <= 128; rows name distinct slots with past + S <= max_ctx (the host checks).  Grid (nwork, n_head).
+void launch_attention_ragged(const RaggedArgs& a, hipStream_t s);
+// out fp32 [B][hidden] = the last-token rows x[t0_b + S_b - 1] of fp32 [T][hidden]; hidden % 4 == 0.
+void launch_ragged_gather(const float* x, const RaggedRow* rows, float* out, int B, int hidden, hipStream_t s);
+
 // ---- Int8 KV cache (bf16 stages with BS_FLAG_INT8_KV; kv_int8.hip) ----
 // The fp32 scales beside the int8 codes of one layer ([max_batch][heads][max_ctx], K and V), and the bf16 staging
 // buffers the QKV epilogue writes a call's new K / V rows to ([B][heads][lmax][hd], slot 0).

@@ -16,6 +16,7 @@
 //   the forward: linear / linear_ln, Tail (which tail a pass ends in, decided once), enqueue_forward
 //   head slices, sampling setters, the per-row sampler and verify-draw buffers, the graph cache
 //   forward_impl (checks, lazy buffers, capture or eager enqueue), bs_forward, bs_forward_score, bs_forward_topk
+//   bs_forward_ragged (rows of different lengths in one pass: attn_ragged.hip)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -311,6 +312,17 @@ struct bs_stage {
   int px_splits = 0;                   // attention_prefix_splits
   std::vector<PrefixRow> px_host;      // [max_batch]
   int px_active = 0;                   // rows that hold a declaration
+  // bs_forward_ragged (attn_ragged.hip): the bf16 staging the QKV epilogue writes a pass's new K / V to, and the
+  // device copy of the pass's rows and work list, one allocation made by the first ragged call (rg_k null: never).
+  // rg_host: the pinned host image the per-call descriptor is built in and copied from, rows first, then the work
+  // list; rg_ev: recorded behind that copy, waited for before the image is rewritten
+  void* rg_k = nullptr;                // bf16 [n_head][max_tokens][hd]
+  void* rg_v = nullptr;
+  RaggedRow* rg_rows = nullptr;        // [max_batch]
+  RaggedWork* rg_work = nullptr;       // [rg_work_cap]
+  int rg_work_cap = 0;                 // max_batch + max_tokens / 64 + 1
+  char* rg_host = nullptr;
+  hipEvent_t rg_ev = nullptr;
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -428,6 +440,8 @@ static void free_stage(bs_stage* s) {
   for (auto e : s->prof.ev) hipEventDestroy(e);
   for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
   for (const OwnedAlloc& a : s->owned) hipFree(a.p);
+  if (s->rg_host) hipHostFree(s->rg_host);
+  if (s->rg_ev) hipEventDestroy(s->rg_ev);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
@@ -2407,4 +2421,195 @@ extern "C" int bs_forward_topk(bs_stage* s, const bs_step* step, const void* in,
   HIP_TRY(hipSetDevice(d.device));
   const TopkIO tk{k, ids, logprobs, lse, logits};
   return forward_impl(s, step, in, nullptr, nullptr, nullptr, stream, &tk);
+}
+
+// ---- Ragged prefill pass (attn_ragged.hip): rows of different lengths, each at its own past position, in one pass
+// over the weights.  The linears run at M = T through the unchanged dispatch; the QKV epilogue sees ONE row of T
+// tokens (slot 0, past 0, max_ctx T) whose "cache" is the staging [n_head][T][hd], as the int8 KV cache redirects it;
+// the attention launch walks a host-built work list and moves the new K / V into the real cache rows; the tail gathers
+// the B last-token rows and runs the M = B head.  Always eager: the grid depends on the host arrays.
+static int ragged_buffers(bs_stage* s) {
+  if (s->rg_k) return BS_OK;
+  const bs_stage_desc& d = s->d;
+  const size_t T = d.max_tokens;
+  const int cap = d.max_batch + d.max_tokens / 64 + 1;
+  const size_t hostb = (size_t)d.max_batch * sizeof(RaggedRow) + (size_t)cap * sizeof(RaggedWork);
+  if (hipHostMalloc((void**)&s->rg_host, hostb) != hipSuccess) {
+    s->rg_host = nullptr;
+    return fail(BS_ERR_OOM, "ragged descriptor host allocation failed");
+  }
+  if (hipEventCreateWithFlags(&s->rg_ev, hipEventDisableTiming) != hipSuccess) {
+    hipHostFree(s->rg_host);
+    s->rg_host = nullptr; s->rg_ev = nullptr;
+    return fail(BS_ERR_DEVICE, "ragged descriptor event");
+  }
+  Carver c;
+  c.piece(&s->rg_k, T * d.hidden * 2);
+  c.piece(&s->rg_v, T * d.hidden * 2);
+  c.piece(&s->rg_rows, (size_t)d.max_batch * sizeof(RaggedRow));
+  c.piece(&s->rg_work, (size_t)cap * sizeof(RaggedWork));
+  if (c.alloc() != Carver::OK) {
+    hipHostFree(s->rg_host);
+    hipEventDestroy(s->rg_ev);
+    s->rg_host = nullptr; s->rg_ev = nullptr;
+    return fail(BS_ERR_OOM, "ragged staging allocation failed (" + std::to_string(c.total) + " B)");
+  }
+  s->owned.push_back({c.base, c.total});
+  s->rg_work_cap = cap;
+  return BS_OK;
+}
+
+extern "C" int bs_forward_ragged(bs_stage* s, const bs_ragged_step* step, const void* in, void* out, float* logits,
+                                 void* stream) {
+  if (!s || !step) return fail(BS_ERR_INVALID, "stage/step is NULL");
+  const bs_stage_desc& d = s->d;
+  const int B = step->rows;
+  if (step->flags & ~(BS_STEP_HOST_IO | BS_STEP_LOGITS))
+    return fail(BS_ERR_INVALID, "a ragged pass takes BS_STEP_HOST_IO and BS_STEP_LOGITS only");
+  if (B < 1 || !step->slots || !step->seq_lens || !step->past_lens)
+    return fail(BS_ERR_INVALID, "rows must be positive and slots / seq_lens / past_lens non-NULL");
+  if (!in || !out) return fail(BS_ERR_INVALID, "in/out is NULL");
+  if (!s->bf16) return fail(BS_ERR_UNSUPPORTED, "bs_forward_ragged needs a BFLOAT16 stage");
+  if (s->kv8) return fail(BS_ERR_UNSUPPORTED, "bs_forward_ragged on an int8 KV cache is not supported");
+  if (s->hd > 128 || s->hd % 8) return fail(BS_ERR_UNSUPPORTED, "bs_forward_ragged needs head_dim % 8 == 0 and <= 128");
+  if (s->n_labels) return fail(BS_ERR_STATE, "bs_forward_ragged on a classifier stage");
+  if (s->top_k > 1) return fail(BS_ERR_STATE, "bs_forward_ragged needs the greedy pick (bs_set_sampling top_k <= 1)");
+  if (d.is_last && (!s->wemb || s->hv0 != 0 || s->hv1 != d.vocab))
+    return fail(BS_ERR_STATE, "bs_forward_ragged on a last stage needs the whole lm_head");
+  const bool want_logits = (step->flags & BS_STEP_LOGITS) != 0;
+  if (want_logits && (!d.is_last || !logits)) return fail(BS_ERR_INVALID, "logits requested on a non-last stage or NULL");
+  if (B > d.max_batch) return fail(BS_ERR_INVALID, "more rows than max_batch");
+  std::vector<RaggedRow> rows(B);
+  std::vector<char> used(d.max_batch, 0);
+  long T = 0;
+  for (int b = 0; b < B; b++) {
+    const int slot = step->slots[b], S = step->seq_lens[b], past = step->past_lens[b];
+    if (slot < 0 || slot >= d.max_batch) return fail(BS_ERR_INVALID, "slot outside max_batch");
+    if (used[slot]) return fail(BS_ERR_INVALID, "slot " + std::to_string(slot) + " named twice");
+    used[slot] = 1;
+    if (S < 1 || past < 0 || (long)past + S > d.max_ctx) return fail(BS_ERR_INVALID, "past_len + seq exceeds max_ctx");
+    rows[b] = RaggedRow{slot, (int)T, S, past};
+    T += S;
+    if (T > d.max_tokens) return fail(BS_ERR_INVALID, "the rows' tokens exceed max_tokens");
+  }
+  for (int b = 0; b < B; b++) {
+    const int slot = rows[b].slot;
+    if (rows_sampled(s, slot, 1) || rows_processed(s, slot, 1) || rows_guided(s, slot, 1) ||
+        (s->px_active && s->px_host[slot].npos > 0))
+      return fail(BS_ERR_STATE, "bs_forward_ragged on a row that holds sampler, processor, guide or shared-prefix state");
+  }
+  const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
+  const int M = (int)T, h = d.hidden, V = d.vocab, hd = s->hd, nh = d.n_head;
+  if (d.is_first && host_io) {
+    const int* ids = (const int*)in;
+    for (int i = 0; i < M; i++)
+      if (ids[i] < 0 || ids[i] >= V) return fail(BS_ERR_INVALID, "token id out of range");
+  }
+  HIP_TRY(hipSetDevice(d.device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  int rc = ragged_buffers(s);
+  if (rc != BS_OK) return rc;
+  // the device copy of the rows' positions (indexed by a row's place in a call) is not this pass's: the next forward
+  // writes its own
+  s->past_next_valid = false;
+  s->hs_last_rows = 0;
+
+  // ---- the descriptor: the rows, then one work item per 64-query tile, the longest key walk first
+  std::vector<RaggedWork> work;
+  for (int b = 0; b < B; b++)
+    for (int qt = 0; qt * 64 < rows[b].S; qt++) work.push_back(RaggedWork{b, qt});
+  auto tiles = [&](const RaggedWork& w) { return (rows[w.row].past + 63) / 64 + w.qtile + 1; };
+  std::stable_sort(work.begin(), work.end(), [&](const RaggedWork& x, const RaggedWork& y) { return tiles(x) > tiles(y); });
+  const size_t rowb = (size_t)B * sizeof(RaggedRow), workb = work.size() * sizeof(RaggedWork);
+  if (s->L > 0) {
+    HIP_TRY(hipEventSynchronize(s->rg_ev));  // the previous pass's copy has read the image (never recorded: returns at once)
+    char* wimg = s->rg_host + (size_t)d.max_batch * sizeof(RaggedRow);
+    std::memcpy(s->rg_host, rows.data(), rowb);
+    std::memcpy(wimg, work.data(), workb);
+    HIP_TRY(hipMemcpyAsync(s->rg_rows, s->rg_host, rowb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->rg_work, wimg, workb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s->rg_ev, st));
+  }
+
+  // ---- input
+  const float* cur = nullptr;
+  if (d.is_first) {
+    const int* ids = (const int*)in;
+    if (host_io) {
+      HIP_TRY(hipMemcpyAsync(s->ids, ids, (size_t)M * 4, hipMemcpyHostToDevice, st));
+      ids = s->ids;
+    }
+    launch_layernorm(1, s->wemb, ids, 0, 0, s->emb_g, s->emb_b, s->xa, 1, M, h, d.ln_eps, st);
+    cur = s->xa;
+  } else if (host_io) {
+    HIP_TRY(hipMemcpyAsync(s->xa, in, (size_t)M * h * 4, hipMemcpyHostToDevice, st));
+    cur = s->xa;
+  } else {
+    cur = (const float*)in;
+  }
+
+  // ---- decoder blocks
+  double keys_sum = 0.0;  // keys the attention reads, over the rows (the profile's algorithmic bytes)
+  for (int b = 0; b < B; b++) keys_sum += (double)rows[b].past + rows[b].S;
+  for (int l = 0; l < s->L; l++) {
+    const Layer& w = s->layers[l];
+    char* kbase = s->kv + l * s->kv_layer_stride;
+    Epi e{};
+    e.kind = EPI_QKV; e.bias = w.t[T_QKV_B]; e.q_out = s->q; e.k_cache = s->rg_k; e.v_cache = s->rg_v;
+    e.hidden = h; e.head_dim = hd; e.max_ctx = M; e.n_head = nh; e.seq = M; e.slot = 0; e.past = 0;
+    e.past_dev = nullptr; e.ldo = 3 * h;
+    linear_ln(s, st, cur, 1, 0, w.t[T_LN1_G], w.t[T_LN1_B], wmat(w, T_QKV_W), M, 3 * h, h, with_splitk(s, e), 4);
+    {
+      ProfScope p(s, st, 3, keys_sum * nh * hd * 2 * s->esz);
+      RaggedArgs a{};
+      a.q = s->q; a.k_cache = kbase; a.v_cache = kbase + s->kv_half; a.k_stage = s->rg_k; a.v_stage = s->rg_v;
+      a.ctx_out = s->ctx; a.slopes = s->slopes; a.rows = s->rg_rows; a.work = s->rg_work; a.nwork = (int)work.size();
+      a.T = M; a.n_head = nh; a.head_dim = hd; a.max_ctx = d.max_ctx; a.hidden = h;
+      a.inv_norm = 1.0f / std::sqrt((float)hd);
+      launch_attention_ragged(a, st);
+    }
+    Epi e2{};
+    e2.kind = EPI_RESID; e2.bias = w.t[T_DENSE_B]; e2.out_f32 = s->attn; e2.resid = cur; e2.ldo = h;
+    linear(s, st, s->ctx, wmat(w, T_DENSE_W), M, h, h, with_splitk(s, e2), 4);
+    Epi e3{};
+    e3.kind = EPI_GELU; e3.bias = w.t[T_FC1_B]; e3.out_act = s->g; e3.ldo = 4 * h;
+    linear_ln(s, st, s->attn, 1, 0, w.t[T_LN2_G], w.t[T_LN2_B], wmat(w, T_FC1_W), M, 4 * h, h, with_splitk(s, e3),
+              (int)s->esz);
+    float* nxt = (!d.is_last && !host_io && l == s->L - 1) ? (float*)out : (cur == s->xa ? s->xb : s->xa);
+    Epi e4{};
+    e4.kind = EPI_RESID; e4.bias = w.t[T_FC2_B]; e4.out_f32 = nxt; e4.resid = s->attn; e4.ldo = h;
+    linear(s, st, s->g, wmat(w, T_FC2_W), M, h, 4 * h, with_splitk(s, e4), 4);
+    cur = nxt;
+  }
+
+  // ---- output
+  if (!d.is_last) {
+    if (host_io) HIP_TRY(hipMemcpyAsync(out, cur, (size_t)M * h * 4, hipMemcpyDeviceToHost, st));
+    else if (s->L == 0) HIP_TRY(hipMemcpyAsync(out, cur, (size_t)M * h * 4, hipMemcpyDeviceToDevice, st));
+  } else {
+    // the B last-token rows -> [B][hidden] (the attention output buffer is free after the last block), then the
+    // M = B head of any forward: ln_f, the tied lm_head, the first index of the largest logit
+    if (s->L == 0) {  // no attention ran: the rows go to the device by themselves
+      HIP_TRY(hipEventSynchronize(s->rg_ev));
+      std::memcpy(s->rg_host, rows.data(), rowb);
+      HIP_TRY(hipMemcpyAsync(s->rg_rows, s->rg_host, rowb, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipEventRecord(s->rg_ev, st));
+    }
+    launch_ragged_gather(cur, s->rg_rows, s->attn, B, h, st);
+    const Tail tail{TAIL_GREEDY, B, V};
+    bs_step hs{};
+    hs.flags = step->flags;
+    float* staged = nullptr;
+    Epi e{};
+    e.kind = EPI_ARGMAX; e.keys = s->keys; e.ldo = V;
+    if ((rc = tail_logits(s, tail, &hs, logits, nullptr, st, &e.logits, &staged)) != BS_OK) return rc;
+    int* tok_out = host_io ? s->tok : (int*)out;
+    linear_ln(s, st, s->attn, 1, 0, s->lnf_g, s->lnf_b, WMat{s->wemb}, B, V, h, with_splitk(s, e), 0);
+    launch_argmax_finalize(s->keys, B, V / 16, nullptr, nullptr, tok_out, st);
+    if ((rc = tail_copy_out(tail, &hs, s->tok, out, staged, logits, st)) != BS_OK) return rc;
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
+  if (host_io) HIP_TRY(hipStreamSynchronize(st));
+  return BS_OK;
 }

@@ -66,6 +66,10 @@ class StageExecutor:
         self._run(lambda h: self.stage.forward(inp, out, batch, seq, slot=slot, past_len=past_len, stream=h),
                   (inp, out))
 
+    def forward_ragged(self, inp, out, slots, seq_lens, past_lens):
+        """A ragged prefill pass (Stage.forward_ragged): rows of different lengths in one pass, ordered like forward."""
+        self._run(lambda h: self.stage.forward_ragged(inp, out, slots, seq_lens, past_lens, stream=h), (inp, out))
+
     def verify(self, inp, out, batch, seq, slot, past_len, logits=None):
         """A BS_STEP_VERIFY pass (Stage.forward(verify=True)): greedy ids of every position on the last stage,
         ordered like forward."""
@@ -419,6 +423,20 @@ class Pipeline:
         if self.is_first and self.world > 1 and not (self.head_split and self.closer == 0):
             _recv(tok, self.closer if self.head_split else self.world - 1, self.pf_group)
         return tok
+
+    def prefill_rows(self, rows, ids, lens):
+        """One ragged pass (bs_forward_ragged) of several rows of micro-batch 0, each from an empty KV row: row rows[k]
+        takes the lens[k] prompt tokens that follow the earlier rows' in `ids` (int32 [sum(lens)]).  One rank holding
+        the whole model (serve.py's ragged admission): the weights stream once for all the rows.  Each row's first
+        generated token lands in self.pf_tok[0][row] (stream-ordered), as prefill_row leaves it; returns them in
+        `rows` order."""
+        if self.world != 1 or self.n_mb != 1 or not hasattr(self.ex, "forward_ragged"):
+            raise ValueError("prefill_rows needs one rank, one micro-batch and the HIP stage executor")
+        self._drain(self.pending[0])
+        toks = torch.empty(len(rows), dtype=torch.int32, device=ids.device)
+        self.ex.forward_ragged(ids, toks, list(rows), list(lens), [0] * len(rows))
+        self.pf_tok[0][torch.tensor(list(rows), dtype=torch.int64, device=ids.device)] = toks
+        return toks
 
     def set_row_sampler(self, mb, row, **state):
         """Per-row sampling (bs_set_row_sampler): give row `row` of micro-batch `mb` the sampler state

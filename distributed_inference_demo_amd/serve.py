@@ -78,6 +78,12 @@ the guide's start state just before the prefill pass, so the guide sees generate
 shared prefix); from then on the device masks the logits ahead of the pick and steps the state behind it.  Each
 sample's record gains the guide's final state, the count of rejected picks and the index of the first EOS.  Combines
 with --sample, the logit processor options, --shared-prefix, --kv int8 and int8 / MXFP4 weights.
+--ragged-admission (opt-in): the samples admitted in the same round -- a wave of up to core_pool_size
+samples, since samples admitted together also finish together -- are prefilled by ONE ragged pass (bs_forward_ragged:
+each row at its own length, the stage's weights streamed once for the wave instead of once per sample), and each
+sample's first token comes from it.  Plain greedy generation on one rank with the HIP stage, bf16, kv bf16: not with
+--sample, the logit processor or guide options, --shared-prefix, --speculate, --sample-speculate, --num-beams, --score,
+--kv int8 or --prefill 0.  Same tokens as without the option up to bf16 rounding of the attention context.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
 unseeded top-k, token ids in (no tokenizer).
@@ -139,6 +145,7 @@ class RunConfig:
     token_bias: tuple = ()            # logit processors: (id, value) pairs or "ID:VALUE" strings, value added to the logit
     guide_file: str = ""              # guided decoding: a JSON token automaton (guide.Guide.to_json) for every sample
     choice: tuple = ()                # guided decoding: token-id sequences ("ID,ID,..." or lists), one is generated, then eos_id
+    ragged_admission: bool = False    # the samples admitted in one round are prefilled by one ragged pass (one rank, greedy)
 
     @property
     def guided(self):
@@ -164,6 +171,16 @@ class RunConfig:
     def __post_init__(self):
         if self.shared_prefix < 0:
             raise ValueError(f"shared_prefix must be >= 0 (got {self.shared_prefix})")
+        if self.ragged_admission:
+            bad = [name for name, on in (
+                ("sample", self.sample), ("the logit processors", self.processors), ("guide_file / choice", self.guided),
+                ("shared_prefix", self.shared_prefix), ("speculate", self.speculate),
+                ("sample_speculate", self.sample_speculate), ("num_beams", self.num_beams), ("score", self.score),
+                ("max_length == 0", self.max_length <= 0), ("kv = 'int8'", self.kv == "int8"),
+                ("prefill = False", not self.prefill), ("dtype != 'bf16'", self.dtype != "bf16")) if on]
+            if bad:
+                raise ValueError("ragged_admission is plain greedy generation with admission prefills on a bf16 stage "
+                                 "with a bf16 KV cache: it excludes " + ", ".join(bad))
         self.bad_token = tuple(int(t) for t in self.bad_token)
         self.token_bias = tuple((int(str(e).split(":")[0]), float(str(e).split(":")[1])) if isinstance(e, str)
                                 else (int(e[0]), float(e[1])) for e in self.token_bias)
@@ -306,6 +323,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
                          "pipeline's schedule is not")
     if cfg.sample and executor_factory is not None:
         raise ValueError("sample is the HIP stage's per-row sampler: not available with an executor_factory")
+    if cfg.ragged_admission and (world != 1 or executor_factory is not None):
+        raise ValueError("ragged_admission runs on one rank (world == 1) with the HIP stage: no executor_factory")
     proc = cfg.processors
     if proc and executor_factory is not None:
         raise ValueError("the logit processors are the HIP stage's: not available with an executor_factory")
@@ -396,6 +415,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
                     feed_mask[t][r] = False
     # ---- init (Ready)
     max_seq = -(-max(lens) // mb) if pf else 1  # a prefill pass of one row fits a micro-batch's hop buffers
+    if cfg.ragged_admission:  # a wave's pass holds every row's whole prompt
+        max_seq = max(lens)
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + cfg.max_length + 1, max_seq=max_seq, seed=cfg.seed,
                                 head_split=cfg.head_split, executor_factory=executor_factory,
@@ -434,7 +455,14 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     for t in range(T + 1):
         for r in release[t] if (fork and cfg.prefix_attention) else ():  # an idle row stands at position 0
             pipe.set_row_prefix(r // mb, r % mb, 0, 0)
-        for i, r in admit[t] if pf else ():
+        if cfg.ragged_admission and admit[t]:  # the round's wave as one ragged pass, each row from an empty KV row
+            wave = admit[t]
+            toks = pipe.prefill_rows([r for _, r in wave], torch.cat([pids[i].view(-1) for i, _ in wave]),
+                                     [lens[i] for i, _ in wave])
+            prefill_tokens += sum(lens[i] for i, _ in wave)
+            for k, (i, _) in enumerate(wave):
+                first[i] = toks[k:k + 1]
+        for i, r in admit[t] if (pf and not cfg.ragged_admission) else ():
             if sampling:  # the row's sampler for this request, ordered before its prefill pass (last rank)
                 pipe.set_row_sampler(r // mb, r % mb, seed=request_seed(cfg.sample_seed, i), **sampling)
             if fork:
@@ -483,6 +511,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     res = {"samples": out, "num_sample": cfg.num_sample, "max_length": cfg.max_length,
            "core_pool_size": cfg.core_pool_size, "stages": world, "prompt_lens": lens, "rounds": T,
            "prefill": pf, "seconds": dt, "tokens_per_s": cfg.num_sample * cfg.max_length / dt}
+    if cfg.ragged_admission:
+        res.update(ragged_admission=True, prefill_passes=sum(1 for a in admit if a), prefill_tokens=prefill_tokens)
     if sampling:
         res.update(sample=True, sample_seed=cfg.sample_seed, **sampling)
     if proc:

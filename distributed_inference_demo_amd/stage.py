@@ -82,6 +82,12 @@ class Step(ctypes.Structure):
                 ("past_lens", ctypes.POINTER(ctypes.c_int32))]
 
 
+class RaggedStep(ctypes.Structure):
+    """bs_ragged_step: rows of different lengths, each at its own past position in its own KV row."""
+    _fields_ = [("rows", ctypes.c_int32), ("flags", ctypes.c_int32), ("slots", ctypes.POINTER(ctypes.c_int32)),
+                ("seq_lens", ctypes.POINTER(ctypes.c_int32)), ("past_lens", ctypes.POINTER(ctypes.c_int32))]
+
+
 class RowSampler(ctypes.Structure):
     """bs_row_sampler: the sampler state of one KV row."""
     _fields_ = [("top_k", ctypes.c_int32), ("top_p", ctypes.c_float), ("temperature", ctypes.c_float),
@@ -125,7 +131,7 @@ EXPORTS = [
     "bs_read_verify_draw", "bs_fork_kv", "bs_copy_kv", "bs_forward_topk", "bs_set_row_prefix",
     "bs_set_row_processor", "bs_note_tokens", "bs_process_logits", "bs_read_row_tokens",
     "bs_load_guide", "bs_unload_guide", "bs_set_row_guide", "bs_advance_row_guide", "bs_guide_logits",
-    "bs_read_row_guide",
+    "bs_read_row_guide", "bs_forward_ragged",
 ]
 
 _LIB = None
@@ -152,6 +158,7 @@ def lib():
         L.bs_init_stage_file.argtypes = [ctypes.POINTER(StageDesc), ctypes.c_char_p, ctypes.POINTER(vp)]
         L.bs_weights_file_probe.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(i32)] * 3
         L.bs_forward.argtypes = [vp, ctypes.POINTER(Step), vp, vp, vp, vp]
+        L.bs_forward_ragged.argtypes = [vp, ctypes.POINTER(RaggedStep), vp, vp, vp, vp]
         L.bs_forward_score.argtypes = [vp, ctypes.POINTER(Step), vp, vp, vp, vp, vp]
         L.bs_reset_kv.argtypes = [vp, i32]
         L.bs_read_kv.argtypes = [vp, i32, i32, i32, i32, vp]
@@ -345,6 +352,43 @@ class Stage:
             for i, r in enumerate(range(slot, slot + batch)):
                 self.past[r] = pasts[i] + seq
         return out
+
+    # ---- ragged prefill pass (bs_forward_ragged; bf16 stages)
+    @staticmethod
+    def _ragged_step(slots, seq_lens, past_lens, flags):
+        n = len(slots)
+        if len(seq_lens) != n or len(past_lens) != n:
+            raise BloomStageError(f"{n} slots, {len(seq_lens)} seq_lens, {len(past_lens)} past_lens")
+        arrs = [(ctypes.c_int32 * max(n, 1))(*[int(v) for v in a]) for a in (slots, seq_lens, past_lens)]
+        st = RaggedStep(n, flags, *arrs)
+        st._keep = arrs
+        return st
+
+    def forward_ragged(self, inp, out, slots, seq_lens, past_lens, logits=None, stream=None):
+        """bs_forward_ragged on device pointers (stream ordered): row b feeds seq_lens[b] new tokens to KV row slots[b]
+        at past_lens[b], the rows' tokens packed in row order (T = sum of seq_lens).  inp: int32 ids [T] on a first
+        stage, else fp32 hidden [T][hidden]; out: fp32 hidden [T][hidden], or on the last stage int32 [rows], the
+        greedy id of each row's last token (logits: fp32 [rows][vocab])."""
+        st = self._ragged_step(slots, seq_lens, past_lens, BS_STEP_LOGITS if logits is not None else 0)
+        _check(lib().bs_forward_ragged(self._h, ctypes.byref(st), _ptr(inp), _ptr(out), _ptr(logits), stream))
+        for r, n, p in zip(slots, seq_lens, past_lens):
+            self.past[int(r)] = int(p) + int(n)
+        return out
+
+    def forward_ragged_host(self, x, slots, seq_lens, past_lens, want_logits=False):
+        """forward_ragged() with numpy in and out: x holds the T packed tokens (ids, or hidden [T][hidden])."""
+        T, B = int(sum(int(n) for n in seq_lens)), len(slots)
+        if self.is_first:
+            x = np.ascontiguousarray(x, dtype=np.int32).reshape(T)
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32).reshape(T, self.hidden)
+        out = np.empty(B, np.int32) if self.is_last else np.empty((T, self.hidden), np.float32)
+        logits = np.empty((B, self.vocab), np.float32) if want_logits else None
+        st = self._ragged_step(slots, seq_lens, past_lens, BS_STEP_HOST_IO | (BS_STEP_LOGITS if want_logits else 0))
+        _check(lib().bs_forward_ragged(self._h, ctypes.byref(st), x.ctypes.data, out.ctypes.data, _ptr(logits), None))
+        for r, n, p in zip(slots, seq_lens, past_lens):
+            self.past[int(r)] = int(p) + int(n)
+        return (out, logits) if want_logits else out
 
     def _advance(self, st, pasts, batch, seq, slot):
         if pasts is None:

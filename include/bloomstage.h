@@ -15,6 +15,7 @@
  *   bs_fork_kv         <- (none: no KV cache, so no shared prompt prefix to reuse)
  *   bs_copy_kv         <- (none: no KV cache, so no hypotheses' rows to reorder)
  *   bs_set_row_prefix  <- (none: no KV cache, so no shared prefix to read once)
+ *   bs_forward_ragged  <- (none: the reference runs one sample per pass; prompts of different lengths share no pass)
  *   bs_forward_score   <- (none: the reference has no scoring task)
  *   bs_forward_topk    <- (none: the reference's tail returns one token, decoding.cpp:24-66, never ranked candidates)
  *   bs_last_error      <- (none: the reference throws C++ exceptions across JNI,
@@ -287,6 +288,40 @@ int bs_forward_score(bs_stage *stage, const bs_step *step, const void *in, const
  * buffer of bs_set_row_sampler, counted under workspace_bytes from then on. */
 int bs_forward_topk(bs_stage *stage, const bs_step *step, const void *in, int32_t k, int32_t *ids, float *logprobs,
                     float *lse, float *logits, void *stream);
+
+/* Ragged prefill pass (bf16 stages): B rows whose prompts differ in length, each at its own past
+ * position in its own KV row, in ONE pass over the stage's weights -- the admission wave of a continuous-batching
+ * server, and the base of chunked prefill (rows with S_b = 1 next to prefilling rows).
+ *   With T = sum S_b, the pass's tokens are packed in row order: row b owns tokens [t0_b, t0_b + S_b), t0_b = sum of
+ *   the earlier rows' S.
+ *   in : first stage -> int32 ids [T]; otherwise fp32 hidden [T][hidden].
+ *   out: a non-last stage writes fp32 hidden [T][hidden]; the last stage writes int32 [B], the first index of the
+ *        largest logit of each row's LAST token (bs_forward's greedy rule; never screened: bs_read_head_screen reports
+ *        *count = -1).  logits (BS_STEP_LOGITS): fp32 [B][vocab].  BS_STEP_HOST_IO as for bs_forward.
+ *   Cache: the pass appends S_b positions to KV row slots[b] at past_lens[b]; nothing at or beyond past_b + S_b of a
+ *   row is written, and no other row is touched.  The linears run once on M = T rows (any weight format); the
+ *   attention is one launch over a work list of (row, 64-query tile) items that also moves the new K / V from their
+ *   staging into the cache (attn_ragged.hip).  Always launched eagerly (the grid depends on the host arrays); results
+ *   are bit-identical from run to run.  The device copy of the rows' positions is marked stale: the next bs_forward
+ *   writes its own.
+ *   The first call allocates the K / V staging (2 * max_tokens * hidden * 2 bytes) and the device work list, counted
+ *   under workspace_bytes from then on; a stage that never calls it allocates and launches nothing new.
+ *   A caller that wants sampling, processors or guides takes the logits and calls bs_sample_logits, bs_process_logits
+ *   or bs_guide_logits.
+ * BS_ERR_INVALID: NULL arrays, rows < 1, a flag other than BS_STEP_HOST_IO | BS_STEP_LOGITS, S_b < 1, past_b < 0,
+ *   past_b + S_b > max_ctx, T > max_tokens, a slot outside max_batch or named twice, logits wanted on a non-last stage.
+ * BS_ERR_UNSUPPORTED: an fp32 stage, a BS_FLAG_INT8_KV stage, head_dim > 128.
+ * BS_ERR_STATE: a classifier stage, after bs_set_sampling chose top_k > 1, a last stage without the whole lm_head, a
+ *   row that holds sampler, processor, guide or shared-prefix state. */
+typedef struct bs_ragged_step {
+  int32_t rows;               /* B >= 1 */
+  int32_t flags;              /* BS_STEP_HOST_IO | BS_STEP_LOGITS */
+  const int32_t *slots;       /* host [B]: distinct KV rows, any order, need not be contiguous */
+  const int32_t *seq_lens;    /* host [B]: S_b >= 1 new tokens of row b */
+  const int32_t *past_lens;   /* host [B]: positions row b already holds */
+} bs_ragged_step;
+int bs_forward_ragged(bs_stage *stage, const bs_ragged_step *step, const void *in, void *out,
+                      float *logits, void *stream);
 
 /* ---- Vocabulary-parallel head (stages with a head slice, or the last stage) ----
  * Argmax keys: uint64 (order(logit) << 32) | (0xFFFFFFFF - vocab_index), where order() maps
