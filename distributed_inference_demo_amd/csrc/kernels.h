@@ -119,6 +119,26 @@ constexpr int kVerifyMaxTokens = 32;
 int attention_verify_split_stride(int n_head, int max_chunks);
 void launch_attention_verify(int is_bf16, const AttnArgs& a, hipStream_t s);
 
+// ---- Tree verify pass (bs_forward_tree, bs_compact_kv; attn_tree.hip) ----
+// One row of a tree pass in the device table (indexed by the row's place in the call): node i attends the pass's
+// nodes whose bit is set in anc[i] (i itself and its ancestors); nibble j of depth is node j's distance to the root.
+constexpr int kTreeMaxNodes = 16;
+constexpr int kTreeMaxRows = kVerifyMaxTokens / 2;
+struct TreeRow {
+  uint16_t anc[kTreeMaxNodes];
+  uint64_t depth;
+};
+// Attention of 2 <= a.S <= kTreeMaxNodes nodes per row, a.B * a.S <= kVerifyMaxTokens, bf16, head_dim % 8 == 0 and
+// <= 128: launch_attention_verify's grid rule, partials (a.part_acc / a.part_ml / a.max_chunks) and tickets, on the
+// matrix cores; node i of row b at cache position past_dev[b] + i, its visible nodes and their ALiBi positions from
+// table[b].  Nothing at or beyond past_dev[b] + a.S is read.
+void launch_attention_tree(const AttnArgs& a, const TreeRow* table, hipStream_t s);
+// Position past + k of row `slot` receives what position past + src[k] held, k < n <= kTreeMaxNodes, in each of the
+// n_lw = layers * 2 bf16 images [max_batch][n_head][max_ctx][head_dim] at `base`: one launch, src by kernel
+// arguments (host, strictly increasing, src[k] >= k).
+void launch_kv_compact(void* base, int n_lw, int n_head, int max_batch, int max_ctx, int head_dim, int slot, int past,
+                       const int* src, int n, hipStream_t s);
+
 // ---- Shared-prefix decode attention (bs_set_row_prefix; attn_prefix.hip) ----
 // One entry of the device table [max_batch]: the row's first npos cached positions hold the bits of row src_slot's
 // (npos == 0: no declaration).

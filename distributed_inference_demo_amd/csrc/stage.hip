@@ -108,8 +108,11 @@ struct GraphKey {
   const void* lse = nullptr;
   int prefix = 0;  // the step's attention takes the shared-prefix route (prefix_route); (src_slot, npos) are not part
                    // of the key: the kernels read them from the device table
+  int tree = 0;    // a tree pass (bs_forward_tree) of seq nodes per row; the trees are not part of the key: the
+                   // attention reads them from the device table
   bool operator==(const GraphKey& o) const {
-    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && tail == o.tail && prefix == o.prefix && in == o.in &&
+    return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && tail == o.tail && prefix == o.prefix &&
+           tree == o.tree && in == o.in &&
            out == o.out && logits == o.logits && st == o.st && k == o.k && logprobs == o.logprobs && lse == o.lse;
   }
 };
@@ -323,6 +326,11 @@ struct bs_stage {
   int rg_work_cap = 0;                 // max_batch + max_tokens / 64 + 1
   char* rg_host = nullptr;
   hipEvent_t rg_ev = nullptr;
+  // bs_forward_tree (attn_tree.hip): the device table of a pass's trees, one allocation made by the first tree call
+  // (tr_table null: never); tr_host / tr_ev: its pinned host image and the event behind the copy, as rg_host / rg_ev
+  TreeRow* tr_table = nullptr;         // [kTreeMaxRows]
+  TreeRow* tr_host = nullptr;
+  hipEvent_t tr_ev = nullptr;
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -442,6 +450,8 @@ static void free_stage(bs_stage* s) {
   for (const OwnedAlloc& a : s->owned) hipFree(a.p);
   if (s->rg_host) hipHostFree(s->rg_host);
   if (s->rg_ev) hipEventDestroy(s->rg_ev);
+  if (s->tr_host) hipHostFree(s->tr_host);
+  if (s->tr_ev) hipEventDestroy(s->tr_ev);
   if (s->own) hipStreamDestroy(s->own);
   delete s;
 }
@@ -1388,7 +1398,8 @@ static int tail_copy_out(const Tail& t, const bs_step* step, const int* tok, voi
 // TAIL_TOPK_LOGPROBS writes (bs_forward_topk).
 static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, const void* in, void* out, float* logits,
                            hipStream_t st, const int* past_dev, const std::vector<int>& pasts,
-                           const ScoreIO* sc = nullptr, const TopkIO* tk = nullptr, bool shared = false) {
+                           const ScoreIO* sc = nullptr, const TopkIO* tk = nullptr, bool shared = false,
+                           bool tree = false) {
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot, past = pasts[0];
   double ctx_sum = 0.0;
@@ -1478,7 +1489,8 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
       ProfScope p(s, st, 3, ctx_sum * nh * hd * 2 * s->esz);
       AttnArgs av = a;
       av.part_acc = s->vf_acc; av.part_ml = s->vf_ml; av.max_chunks = s->vf_stride;
-      launch_attention_verify(s->bf16, av, st);
+      if (tree) launch_attention_tree(av, s->tr_table, st);  // the same grid and partials on the matrix cores (attn_tree.hip)
+      else launch_attention_verify(s->bf16, av, st);
     } else if (!s->kv8) {
       ProfScope p(s, st, 3, ctx_sum * nh * hd * 2 * s->esz);
       launch_attention(s->bf16, a, st);
@@ -2222,7 +2234,7 @@ static int topk_buffers(bs_stage* s) {
 // bs_forward and bs_forward_score (sc non-null): argument checks, the rows' positions on the device, the enqueue
 // (captured or eager) and the bookkeeping of what the pass's last kernel left in past_dev.
 static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, const ScoreIO* sc,
-                        void* stream, const TopkIO* tk = nullptr) {
+                        void* stream, const TopkIO* tk = nullptr, const TreeRow* tree = nullptr) {
   if (!s || !step) return fail(BS_ERR_INVALID, "stage/step is NULL");
   const bs_stage_desc& d = s->d;
   const int B = step->batch, S = step->seq, slot = step->slot;
@@ -2251,8 +2263,11 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     return fail(BS_ERR_INVALID, "BS_STEP_VERIFY_DRAW is valid only together with BS_STEP_VERIFY on bs_forward");
   if (verify) {
     if (sc) return fail(BS_ERR_INVALID, "BS_STEP_VERIFY is not valid for a scoring pass");
-    if (S < 2 || S > 8 || M > kVerifyMaxTokens)
-      return fail(BS_ERR_INVALID, "a verify pass needs 2 <= seq <= 8 and batch * seq <= 32");
+    if (S < 2 || S > (tree ? kTreeMaxNodes : 8) || M > kVerifyMaxTokens)
+      return fail(BS_ERR_INVALID, tree ? "a tree pass needs 2 <= nodes <= 16 and batch * nodes <= 32"
+                                       : "a verify pass needs 2 <= seq <= 8 and batch * seq <= 32");
+    if (tree && !s->bf16) return fail(BS_ERR_UNSUPPORTED, "bs_forward_tree needs a BFLOAT16 stage");
+    if (tree && s->hd % 8) return fail(BS_ERR_UNSUPPORTED, "bs_forward_tree needs head_dim % 8 == 0");
     if (s->kv8) return fail(BS_ERR_UNSUPPORTED, "BS_STEP_VERIFY on an int8 KV cache is not supported");
     if (s->hd > 128) return fail(BS_ERR_UNSUPPORTED, "BS_STEP_VERIFY needs head_dim <= 128");
     if (s->n_labels) return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a classifier stage");
@@ -2293,6 +2308,25 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     s->owned.push_back({c.base, c.total});
     s->vf_stride = stride;
   }
+  if (tree && !s->tr_table) {  // first tree call: the device table of the trees, its pinned image and its event
+    if (hipHostMalloc((void**)&s->tr_host, kTreeMaxRows * sizeof(TreeRow)) != hipSuccess) {
+      s->tr_host = nullptr;
+      return fail(BS_ERR_OOM, "tree table host allocation failed");
+    }
+    if (!s->tr_ev && hipEventCreateWithFlags(&s->tr_ev, hipEventDisableTiming) != hipSuccess) {
+      hipHostFree(s->tr_host);
+      s->tr_host = nullptr; s->tr_ev = nullptr;
+      return fail(BS_ERR_DEVICE, "tree table event");
+    }
+    Carver c;
+    c.piece(&s->tr_table, kTreeMaxRows * sizeof(TreeRow));
+    if (c.alloc() != Carver::OK) {
+      hipHostFree(s->tr_host);
+      s->tr_host = nullptr;
+      return fail(BS_ERR_OOM, "tree table allocation failed");
+    }
+    s->owned.push_back({c.base, c.total});
+  }
   if (tail.kind == TAIL_TOPK_LOGPROBS) {
     int rc = topk_buffers(s);
     if (rc != BS_OK) return rc;
@@ -2315,13 +2349,14 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   const bool shared = prefix_route(s, step, pasts);
   GraphKey key{B, S, slot, step->flags, tail.kind, in, out, logits, st};
   key.prefix = shared ? 1 : 0;
+  key.tree = tree ? 1 : 0;
   if (tk) { key.out = tk->ids; key.logits = tk->logits; key.k = tk->k; key.logprobs = tk->logprobs; key.lse = tk->lse; }
   if (graph && !(exec = find_graph(s, key))) {
     hipGraph_t gr = nullptr;
     BS_TRACE("hipStreamBeginCapture");
     HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
     BS_TRACE("enqueue_forward (capturing)");
-    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, nullptr, tk, shared);
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, nullptr, tk, shared, tree != nullptr);
     BS_TRACE("hipStreamEndCapture");
     hipError_t ce = hipStreamEndCapture(st, &gr);
     if (rc != BS_OK) { if (gr) hipGraphDestroy(gr); return rc; }
@@ -2333,6 +2368,12 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     if (ie != hipSuccess) return fail(BS_ERR_DEVICE, std::string("graph instantiate: ") + hipGetErrorString(ie));
     if ((rc = insert_graph(s, key, exec)) != BS_OK) return rc;
   }
+  if (tree) {  // the pass's trees -> the device table, ahead of the launch or the replay that reads it
+    HIP_TRY(hipEventSynchronize(s->tr_ev));  // the previous pass's copy has read the image (never recorded: returns at once)
+    std::memcpy(s->tr_host, tree, (size_t)B * sizeof(TreeRow));
+    HIP_TRY(hipMemcpyAsync(s->tr_table, s->tr_host, (size_t)B * sizeof(TreeRow), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(s->tr_ev, st));
+  }
   if (!past_matches) {
     BS_TRACE("set_past launch");
     launch_set_past(s->past_dev, pasts.data(), B, st);
@@ -2342,7 +2383,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
     HIP_TRY(hipGraphLaunch(exec, st));
   } else {
     BS_TRACE("enqueue_forward (eager)");
-    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, sc, tk, shared);
+    int rc = enqueue_forward(s, step, tail, in, out, logits, st, s->past_dev, pasts, sc, tk, shared, tree != nullptr);
     if (rc != BS_OK) return rc;
   }
   BS_TRACE("hipGetLastError");
@@ -2369,6 +2410,65 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
 
 extern "C" int bs_forward(bs_stage* s, const bs_step* step, const void* in, void* out, float* logits, void* stream) {
   return forward_impl(s, step, in, out, logits, nullptr, stream);
+}
+
+// Tree verify pass (attn_tree.hip): a BS_STEP_VERIFY pass of seq = nodes whose attention takes its mask and ALiBi
+// positions from the trees.  Everything but the attention launch is forward_impl's verify route.
+extern "C" int bs_forward_tree(bs_stage* s, const bs_tree_step* step, const void* in, void* out, float* logits,
+                               void* stream) {
+  if (!s || !step) return fail(BS_ERR_INVALID, "stage/step is NULL");
+  const int B = step->batch, N = step->nodes;
+  if (step->flags & ~(BS_STEP_HOST_IO | BS_STEP_LOGITS))
+    return fail(BS_ERR_INVALID, "a tree pass takes BS_STEP_HOST_IO and BS_STEP_LOGITS only");
+  if (B < 1 || N < 2 || N > kTreeMaxNodes || B * N > kVerifyMaxTokens)
+    return fail(BS_ERR_INVALID, "a tree pass needs 2 <= nodes <= 16 and batch * nodes <= 32");
+  if (!step->past_lens || !step->parents) return fail(BS_ERR_INVALID, "past_lens / parents is NULL");
+  if (step->slot < 0 || step->slot + B > s->d.max_batch) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  TreeRow rows[kTreeMaxRows];
+  for (int b = 0; b < B; b++) {
+    const int32_t* par = step->parents + (size_t)b * N;
+    TreeRow& t = rows[b];
+    std::memset(&t, 0, sizeof(t));
+    int depth[kTreeMaxNodes];
+    for (int i = 0; i < N; i++) {
+      if (i == 0 ? par[0] != -1 : (par[i] < 0 || par[i] >= i))
+        return fail(BS_ERR_INVALID, "parents: node 0 is the root (-1), every other node names an earlier node");
+      depth[i] = i ? depth[par[i]] + 1 : 0;
+      t.anc[i] = (uint16_t)((i ? t.anc[par[i]] : 0u) | (1u << i));
+      t.depth |= (uint64_t)depth[i] << (4 * i);
+    }
+  }
+  for (int b = 0; b < B; b++)
+    if (s->px_active && s->px_host[step->slot + b].npos > 0)
+      return fail(BS_ERR_STATE, "bs_forward_tree on a row that holds shared-prefix state");
+  bs_step vs{};
+  vs.batch = B; vs.seq = N; vs.slot = step->slot; vs.past_len = step->past_lens[0];
+  vs.flags = step->flags | BS_STEP_VERIFY;
+  vs.past_lens = step->past_lens;
+  return forward_impl(s, &vs, in, out, logits, nullptr, stream, nullptr, rows);
+}
+
+// In-row KV compaction behind a tree pass (attn_tree.hip kv_compact_kernel): one launch for every layer, K and V.
+// Enqueues only, as bs_fork_kv.
+extern "C" int bs_compact_kv(bs_stage* s, int32_t slot, int32_t past, const int32_t* src, int32_t n, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot outside max_batch");
+  if (n < 0 || n > kTreeMaxNodes || past < 0 || (n > 0 && !src)) return fail(BS_ERR_INVALID, "n outside [0, 16], negative past or NULL src");
+  bool identity = true;
+  for (int k = 0; k < n; k++) {
+    if (src[k] < k || (k && src[k] <= src[k - 1])) return fail(BS_ERR_INVALID, "src must be strictly increasing with src[k] >= k");
+    identity = identity && src[k] == k;
+  }
+  if (n && (long)past + src[n - 1] >= s->d.max_ctx) return fail(BS_ERR_INVALID, "past + src beyond max_ctx");
+  if (!s->bf16 || s->kv8) return fail(BS_ERR_UNSUPPORTED, "bs_compact_kv needs a BFLOAT16 stage with a bf16 KV cache");
+  if (s->hd > 128 || s->hd % 8) return fail(BS_ERR_UNSUPPORTED, "bs_compact_kv needs head_dim % 8 == 0 and <= 128");
+  if (identity || s->L <= 0) return BS_OK;
+  HIP_TRY(hipSetDevice(s->d.device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->own;
+  launch_kv_compact(s->kv, 2 * s->L, s->d.n_head, s->d.max_batch, s->d.max_ctx, s->hd, slot, past, src, n, st);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kv compact: ") + hipGetErrorString(err));
+  return BS_OK;
 }
 
 extern "C" int bs_forward_score(bs_stage* s, const bs_step* step, const void* in, const int32_t* targets,

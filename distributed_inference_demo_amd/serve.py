@@ -36,6 +36,10 @@ same vocabulary, e.g. the target's "-int8" variant) proposes up to K tokens a ro
 the target emits the agreeing prefix plus one token.  The tokens are plain greedy decoding's; rank 0 also returns
 the acceptance statistics.  One stage only: the ranks of a pipeline derive their schedule from the prompt lengths
 alone, and how many tokens a pass accepts depends on the data.
+--speculate-tree N (2..16, with --draft ngram) is --speculate's loop with a TREE of N - 1 drafts a round: the n-gram
+tree drafter merges the continuations of every earlier occurrence of the repeated suffix, one bs_forward_tree pass
+verifies all of them, the longest agreeing root-to-leaf path is emitted and bs_compact_kv makes its K / V contiguous.
+Routed like --speculate with the same exclusions; it excludes --speculate itself, sampling and draft models.
 --sample is per-row nucleus sampling (bs_set_row_sampler; the reference's tail draws an unseeded top-k sample,
 decoding.cpp:24-66): the last rank gives the row a sample is admitted into the state (--top-k, --top-p, --temperature,
 request_seed(--sample-seed, sample id)) just before the sample's prefill pass, so its first generated token is already
@@ -146,6 +150,7 @@ class RunConfig:
     guide_file: str = ""              # guided decoding: a JSON token automaton (guide.Guide.to_json) for every sample
     choice: tuple = ()                # guided decoding: token-id sequences ("ID,ID,..." or lists), one is generated, then eos_id
     ragged_admission: bool = False    # the samples admitted in one round are prefilled by one ragged pass (one rank, greedy)
+    speculate_tree: int = 0           # tree speculative decoding: nodes per tree pass, 2..16 (0 = off; one GPU, draft ngram)
 
     @property
     def guided(self):
@@ -181,6 +186,18 @@ class RunConfig:
             if bad:
                 raise ValueError("ragged_admission is plain greedy generation with admission prefills on a bf16 stage "
                                  "with a bf16 KV cache: it excludes " + ", ".join(bad))
+        if self.speculate_tree:
+            if not 2 <= self.speculate_tree <= 16:
+                raise ValueError(f"speculate_tree must be in [2, 16] (got {self.speculate_tree}): a tree pass holds 16 nodes")
+            bad = [name for name, on in (
+                ("speculate", self.speculate), ("sample", self.sample), ("sample_speculate", self.sample_speculate),
+                ("a draft model (draft != 'ngram')", self.draft != "ngram"), ("the logit processors", self.processors),
+                ("guide_file / choice", self.guided), ("shared_prefix", self.shared_prefix), ("num_beams", self.num_beams),
+                ("score", self.score), ("max_length == 0", self.max_length <= 0), ("kv = 'int8'", self.kv == "int8"),
+                ("ragged_admission", self.ragged_admission), ("dtype != 'bf16'", self.dtype != "bf16")) if on]
+            if bad:
+                raise ValueError("speculate_tree is greedy tree speculative decoding with the n-gram drafter on a bf16 "
+                                 "stage with a bf16 KV cache: it excludes " + ", ".join(bad))
         self.bad_token = tuple(int(t) for t in self.bad_token)
         self.token_bias = tuple((int(str(e).split(":")[0]), float(str(e).split(":")[1])) if isinstance(e, str)
                                 else (int(e[0]), float(e[1])) for e in self.token_bias)
@@ -315,7 +332,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     lengths (None: synthetic).  Returns {"samples": [[max_length ids] per sample], ...} on rank 0,
     None elsewhere.  Collective: every rank calls it with the same cfg."""
     say = log if (log is not None and rank == 0) else (lambda *_: None)
-    if (cfg.speculate or cfg.sample_speculate) and world != 1:
+    if (cfg.speculate or cfg.sample_speculate or cfg.speculate_tree) and world != 1:
         raise ValueError("speculative decoding runs on one stage (world == 1): acceptance is data-dependent, the "
                          "pipeline's schedule is not")
     if cfg.num_beams and world != 1:
@@ -378,7 +395,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
         return _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
     if cfg.max_length == 0:
         return _classify_run(cfg, model, rank, world, device, prompts, lens, executor_factory, say)
-    if cfg.speculate or cfg.sample_speculate:
+    if cfg.speculate or cfg.sample_speculate or cfg.speculate_tree:
         return _spec_run(cfg, model, device, prompts, lens, say)
     if cfg.num_beams:
         return _beam_run(cfg, model, device, prompts, lens, say)
@@ -649,8 +666,10 @@ def _spec_run(cfg, model, device, prompts, lens, say):
     """--speculate K (world == 1): the whole model as one stage, the samples decoded one after another in KV row 0
     by speculative.SpeculativeDecoder.  Returns the generation task's record plus the acceptance statistics.
     --sample --sample-speculate K: the same loop, sample i decoded with the sampler state of the config and
-    request_seed(sample_seed, i); a model drafter holds the same state."""
-    from .speculative import NgramDrafter, SpeculativeDecoder, StageChain, StageDrafter
+    request_seed(sample_seed, i); a model drafter holds the same state.
+    --speculate-tree N: the same loop with speculative.TreeSpeculativeDecoder and the n-gram tree drafter."""
+    from .speculative import (NgramDrafter, NgramTreeDrafter, SpeculativeDecoder, StageChain, StageDrafter,
+                              TreeSpeculativeDecoder)
     from .stage import Stage
     dev = device.index if device.type == "cuda" and device.index is not None else 0
     max_ctx = max(lens) + cfg.max_length + 1
@@ -663,7 +682,9 @@ def _spec_run(cfg, model, device, prompts, lens, say):
     k = cfg.sample_speculate or cfg.speculate
     sampling = ({"top_k": cfg.top_k, "top_p": cfg.top_p, "temperature": cfg.temperature} if cfg.sample_speculate
                 else None)
-    if cfg.draft == "ngram":
+    if cfg.speculate_tree:
+        drafter = NgramTreeDrafter(cfg.speculate_tree)
+    elif cfg.draft == "ngram":
         drafter = NgramDrafter(k)
     else:
         dm = config.get(cfg.draft) if isinstance(cfg.draft, str) else cfg.draft
@@ -680,7 +701,9 @@ def _spec_run(cfg, model, device, prompts, lens, say):
         sampler = dict(sampling, seed=request_seed(cfg.sample_seed, i)) if sampling else None
         if sampler and isinstance(drafter, StageDrafter):
             drafter.chain.set_sampler(sampler)  # the draft row draws with this request's u
-        toks, st = SpeculativeDecoder(chain, drafter, k, sampler=sampler).generate(p, cfg.max_length)
+        dec = (TreeSpeculativeDecoder(chain, drafter, cfg.speculate_tree) if cfg.speculate_tree
+               else SpeculativeDecoder(chain, drafter, k, sampler=sampler))
+        toks, st = dec.generate(p, cfg.max_length)
         out.append(toks)
         for name in tot:
             tot[name] += st[name]
@@ -691,6 +714,8 @@ def _spec_run(cfg, model, device, prompts, lens, say):
            "core_pool_size": cfg.core_pool_size, "stages": 1, "prompt_lens": lens, "seconds": dt,
            "tokens_per_s": cfg.num_sample * cfg.max_length / dt, "speculate": cfg.speculate, "draft": cfg.draft, **tot,
            "acceptance_rate": tot["accepted"] / tot["drafted"] if tot["drafted"] else None}
+    if cfg.speculate_tree:
+        res.update(speculate_tree=cfg.speculate_tree)
     if sampling:
         res.update(sample=True, sample_seed=cfg.sample_seed, sample_speculate=k, **sampling)
     say(STATES[2], {k: v for k, v in res.items() if k != "samples"})

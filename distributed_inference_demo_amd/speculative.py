@@ -10,6 +10,14 @@ exactly the tokens plain greedy decoding produces.
                                   variant of the target) with its own KV row
     SpeculativeDecoder(stages, drafter, k).generate(prompt, max_new)
 
+Tree verification (greedy; bs_forward_tree + bs_compact_kv): a drafter proposes a TREE of
+drafts under the last token, one pass returns the greedy token after every node, and the longest root-to-leaf path
+the target agrees with is emitted, so one wrong draft no longer throws away its siblings' continuations.
+
+    accept_tree(tokens, parents, top)       the acceptance rule, a pure function
+    NgramTreeDrafter(n_nodes, n_max)        prompt lookup over every earlier occurrence, merged into a trie
+    TreeSpeculativeDecoder(stages, drafter, n_nodes).generate(prompt, max_new)
+
 Sampled speculative decoding (sampler = {"top_k", "top_p", "temperature", "seed"} on the decoder, and on a
 StageDrafter): the target's KV row holds that per-row sampler state, plain steps sample, and a verify pass runs with
 BS_STEP_VERIFY_DRAW: it returns the row's own DRAW at every position.  A draw depends on (seed, position, logits)
@@ -141,6 +149,141 @@ class StageChain:
         """Feed 2..8 tokens at position `past`; the greedy token after each of them, or with draw=True
         (BS_STEP_VERIFY_DRAW) the row sampler's draw after each of them."""
         return self._run(list(ids), past, True, draw)
+
+    def verify_tree(self, tokens, parents, past):
+        """One bs_forward_tree pass of row 0: node i (token tokens[i], parent parents[i], node 0 the row's last token)
+        at cache position past + i; the greedy token after every node."""
+        n = len(tokens)
+        for st in self.stages:
+            st.past[0] = past
+        if self.host_io:
+            x = np.asarray(tokens, np.int32).reshape(1, n)
+            for st in self.stages:
+                x = st.forward_tree_host(x, [list(parents)], slot=0, past_len=[past])
+            return [int(t) for t in np.asarray(x).reshape(-1)]
+        import torch
+        dids, hid, out = self._buffers(n)
+        with torch.cuda.stream(self._stream):
+            dids.copy_(torch.tensor(list(tokens), dtype=torch.int32))
+            x = dids
+            for i, st in enumerate(self.stages):
+                y = out if i == len(self.stages) - 1 else hid[i]
+                st.forward_tree(x, y, [list(parents)], slot=0, past_len=[past], stream=self._stream.cuda_stream)
+                x = y
+            res = out[:n].cpu()
+        return [int(t) for t in res.tolist()]
+
+    def compact(self, past, src):
+        """bs_compact_kv of row 0 on every stage, ordered on the chain's stream: position past + k <- past + src[k]."""
+        stream = None if self.host_io or self._stream is None else self._stream.cuda_stream
+        for st in self.stages:
+            st.compact_kv(0, past, src, stream=stream)
+
+
+def accept_tree(tokens, parents, top):
+    """The acceptance rule of a tree pass: node i holds tokens[i] (node 0: the row's last token), parents[i] < i its
+    parent, top[i] the target's greedy token after node i.  Starting at the root, move to the first child (lowest
+    index) whose token equals top[node], until there is none.  Returns (visited node indices, emitted tokens): the
+    path from the root and top of every node on it -- the accepted drafts and the target's own next token."""
+    tokens, parents, top = [int(t) for t in tokens], [int(p) for p in parents], [int(t) for t in top]
+    if not (len(tokens) == len(parents) == len(top)) or not tokens:
+        raise ValueError(f"{len(tokens)} tokens, {len(parents)} parents, {len(top)} verified nodes")
+    node, visited = 0, [0]
+    while True:
+        nxt = next((i for i in range(node + 1, len(tokens)) if parents[i] == node and tokens[i] == top[node]), None)
+        if nxt is None:
+            return visited, [top[i] for i in visited]
+        visited.append(nxt)
+        node = nxt
+
+
+class NgramTreeDrafter:
+    """Prompt lookup with every candidate: the longest suffix of the history (n_max down to 1 tokens) that occurred
+    earlier; the continuations of its earlier occurrences, most recent first, merged into a trie under the history's
+    last token until the trie holds n_nodes nodes.  propose() returns (tokens, parents) with node 0 the last token,
+    or None when nothing repeats."""
+
+    def __init__(self, n_nodes, n_max=3):
+        if not 2 <= n_nodes <= 16 or n_max < 1:
+            raise ValueError("n_nodes must be in [2, 16] and n_max >= 1")
+        self.n_nodes, self.n_max = n_nodes, n_max
+
+    def propose(self, history, n_nodes=None):
+        cap = self.n_nodes if n_nodes is None else min(n_nodes, self.n_nodes)
+        h = [int(t) for t in history]
+        if cap < 2 or len(h) < 2:
+            return None
+        for n in range(min(self.n_max, len(h) - 1), 0, -1):
+            suffix = h[-n:]
+            starts = [i for i in range(len(h) - n - 1, -1, -1) if h[i:i + n] == suffix]
+            if not starts:
+                continue
+            tokens, parents = [h[-1]], [-1]
+            for i in starts:
+                node = 0
+                for tok in h[i + n:i + n + cap - 1]:
+                    child = next((c for c in range(node + 1, len(tokens)) if parents[c] == node and tokens[c] == tok), None)
+                    if child is None:
+                        if len(tokens) == cap:
+                            break
+                        tokens.append(tok)
+                        parents.append(node)
+                        child = len(tokens) - 1
+                    node = child
+                if len(tokens) == cap:
+                    break
+            return tokens, parents
+        return None
+
+
+class TreeSpeculativeDecoder:
+    """Greedy generation of one sample (KV row 0) with a tree of n_nodes - 1 drafts a pass.  Each round the drafter
+    proposes (tokens, parents); one bs_forward_tree pass (the tree padded to the pass's node count with children of
+    the root, so one captured graph serves every round) returns the greedy token after every node; accept_tree()
+    picks the path; bs_compact_kv moves the visited non-root nodes' K / V behind the root on every stage; the position
+    advances by the emitted tokens.  Without a proposal the round is a plain S = 1 step.  The tokens equal plain
+    greedy decoding's under SpeculativeDecoder's margin condition."""
+
+    def __init__(self, stages, drafter, n_nodes, host_io=False):
+        if not 2 <= n_nodes <= 16:
+            raise ValueError("n_nodes must be in [2, 16] (a tree pass holds at most 16 nodes)")
+        self.chain = stages if isinstance(stages, StageChain) else StageChain(stages, host_io=host_io)
+        self.drafter, self.n_nodes = drafter, n_nodes
+
+    def generate(self, prompt, max_new):
+        """Returns (tokens [max_new], {"passes": tree passes, "drafted": draft nodes in them, "accepted": draft nodes
+        that were emitted, "plain_steps": S = 1 rounds})."""
+        prompt = [int(t) for t in prompt]
+        if not prompt or max_new < 1:
+            raise ValueError("generate needs a prompt and max_new >= 1")
+        if len(prompt) + max_new > self.chain.max_ctx:
+            raise ValueError(f"prompt ({len(prompt)}) + max_new ({max_new}) exceed max_ctx ({self.chain.max_ctx})")
+        stats = {"passes": 0, "drafted": 0, "accepted": 0, "plain_steps": 0}
+        hist = prompt + [self.chain.prefill(prompt, 0)]
+        pos = len(prompt)  # positions the row holds; hist[pos:] is not cached yet (always one token)
+        while len(hist) - len(prompt) < max_new:
+            left = max_new - (len(hist) - len(prompt))
+            n = min(self.n_nodes, self.chain.max_ctx - pos)  # the pass writes n positions
+            tree = self.drafter.propose(hist, n) if n >= 2 and left >= 2 else None
+            if not tree:
+                emitted = [self.chain.step(hist[-1], pos)]
+                stats["plain_steps"] += 1
+            else:
+                tokens, parents = [int(t) for t in tree[0]][:n], [int(p) for p in tree[1]][:n]
+                real = len(tokens)
+                pad = n - real  # extra children of the root: nothing sees them, their results are ignored
+                top = self.chain.verify_tree(tokens + [tokens[0]] * pad, parents + [0] * pad, pos)
+                visited, emitted = accept_tree(tokens, parents, top[:real])
+                visited, emitted = visited[:left], emitted[:left]
+                self.chain.compact(pos + 1, [i - 1 for i in visited[1:]])
+                stats["passes"] += 1
+                stats["drafted"] += real - 1
+                stats["accepted"] += len(visited) - 1
+            pos += len(emitted)
+            hist += emitted
+        for st in self.chain.stages:
+            st.past[0] = pos
+        return hist[len(prompt):], stats
 
 
 class StageDrafter:

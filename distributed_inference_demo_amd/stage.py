@@ -88,6 +88,13 @@ class RaggedStep(ctypes.Structure):
                 ("seq_lens", ctypes.POINTER(ctypes.c_int32)), ("past_lens", ctypes.POINTER(ctypes.c_int32))]
 
 
+class TreeStep(ctypes.Structure):
+    """bs_tree_step: N draft-tree nodes per row; parents [B][N], node 0 the root (-1)."""
+    _fields_ = [("batch", ctypes.c_int32), ("nodes", ctypes.c_int32), ("slot", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("past_lens", ctypes.POINTER(ctypes.c_int32)),
+                ("parents", ctypes.POINTER(ctypes.c_int32))]
+
+
 class RowSampler(ctypes.Structure):
     """bs_row_sampler: the sampler state of one KV row."""
     _fields_ = [("top_k", ctypes.c_int32), ("top_p", ctypes.c_float), ("temperature", ctypes.c_float),
@@ -131,7 +138,7 @@ EXPORTS = [
     "bs_read_verify_draw", "bs_fork_kv", "bs_copy_kv", "bs_forward_topk", "bs_set_row_prefix",
     "bs_set_row_processor", "bs_note_tokens", "bs_process_logits", "bs_read_row_tokens",
     "bs_load_guide", "bs_unload_guide", "bs_set_row_guide", "bs_advance_row_guide", "bs_guide_logits",
-    "bs_read_row_guide", "bs_forward_ragged",
+    "bs_read_row_guide", "bs_forward_ragged", "bs_forward_tree", "bs_compact_kv",
 ]
 
 _LIB = None
@@ -159,6 +166,8 @@ def lib():
         L.bs_weights_file_probe.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(i32)] * 3
         L.bs_forward.argtypes = [vp, ctypes.POINTER(Step), vp, vp, vp, vp]
         L.bs_forward_ragged.argtypes = [vp, ctypes.POINTER(RaggedStep), vp, vp, vp, vp]
+        L.bs_forward_tree.argtypes = [vp, ctypes.POINTER(TreeStep), vp, vp, vp, vp]
+        L.bs_compact_kv.argtypes = [vp, i32, i32, ctypes.POINTER(i32), i32, vp]
         L.bs_forward_score.argtypes = [vp, ctypes.POINTER(Step), vp, vp, vp, vp, vp]
         L.bs_reset_kv.argtypes = [vp, i32]
         L.bs_read_kv.argtypes = [vp, i32, i32, i32, i32, vp]
@@ -389,6 +398,56 @@ class Stage:
         for r, n, p in zip(slots, seq_lens, past_lens):
             self.past[int(r)] = int(p) + int(n)
         return (out, logits) if want_logits else out
+
+    # ---- tree verify pass (bs_forward_tree; bf16 stages)
+    def _tree_step(self, parents, slot, past_lens, flags):
+        par = np.ascontiguousarray(parents, dtype=np.int32)
+        par = par.reshape(1, -1) if par.ndim == 1 else par
+        batch, nodes = par.shape
+        if past_lens is None:
+            past_lens = self.past[slot:slot + batch]
+        pasts = [int(past_lens)] * batch if np.ndim(past_lens) == 0 else [int(p) for p in past_lens]
+        if len(pasts) != batch:
+            raise BloomStageError(f"{len(pasts)} past lengths for {batch} rows")
+        parr = (ctypes.c_int32 * batch)(*pasts)
+        st = TreeStep(batch, nodes, slot, flags, parr, par.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        st._keep = (parr, par)
+        return st, pasts
+
+    def forward_tree(self, inp, out, parents, slot=0, past_len=None, logits=None, stream=None):
+        """bs_forward_tree on device pointers (stream ordered; replays a captured graph): parents int32 [batch][nodes]
+        (node 0 the root, -1; parents[i] < i), node i of row b at cache position past_b + i attending the cached past
+        and its own ancestors.  inp: int32 ids [batch][nodes] on a first stage, else fp32 hidden; out: fp32 hidden
+        [batch][nodes][hidden], or on the last stage int32 [batch][nodes], the greedy id after every node (logits:
+        fp32 [batch][nodes][vocab]).  The rows then stand at past_b + nodes: compact_kv() the accepted path and
+        rollback()."""
+        st, pasts = self._tree_step(parents, slot, past_len, BS_STEP_LOGITS if logits is not None else 0)
+        _check(lib().bs_forward_tree(self._h, ctypes.byref(st), _ptr(inp), _ptr(out), _ptr(logits), stream))
+        self._advance(None, pasts, st.batch, st.nodes, slot)
+        return out
+
+    def forward_tree_host(self, x, parents, slot=0, past_len=None, want_logits=False):
+        """forward_tree() with numpy in and out."""
+        st, pasts = self._tree_step(parents, slot, past_len, BS_STEP_HOST_IO | (BS_STEP_LOGITS if want_logits else 0))
+        B, N = st.batch, st.nodes
+        if self.is_first:
+            x = np.ascontiguousarray(x, dtype=np.int32).reshape(B, N)
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32).reshape(B, N, self.hidden)
+        out = np.empty((B, N), np.int32) if self.is_last else np.empty((B, N, self.hidden), np.float32)
+        logits = np.empty((B, N, self.vocab), np.float32) if want_logits else None
+        _check(lib().bs_forward_tree(self._h, ctypes.byref(st), x.ctypes.data, out.ctypes.data, _ptr(logits), None))
+        self._advance(None, pasts, B, N, slot)
+        return (out, logits) if want_logits else out
+
+    def compact_kv(self, slot, past, src, stream=None):
+        """bs_compact_kv: position past + k of KV row `slot` receives what position past + src[k] held (every layer,
+        K and V), src strictly increasing with src[k] >= k and at most 16 entries.  Stream ordered; the row then
+        stands at past + len(src)."""
+        src = [int(v) for v in src]
+        arr = (ctypes.c_int32 * max(len(src), 1))(*src)
+        _check(lib().bs_compact_kv(self._h, int(slot), int(past), arr, len(src), stream))
+        self.past[slot] = int(past) + len(src)
 
     def _advance(self, st, pasts, batch, seq, slot):
         if pasts is None:

@@ -16,6 +16,8 @@
  *   bs_copy_kv         <- (none: no KV cache, so no hypotheses' rows to reorder)
  *   bs_set_row_prefix  <- (none: no KV cache, so no shared prefix to read once)
  *   bs_forward_ragged  <- (none: the reference runs one sample per pass; prompts of different lengths share no pass)
+ *   bs_forward_tree, bs_compact_kv
+ *                      <- (none: the reference decodes one token per pass; no drafts to verify)
  *   bs_forward_score   <- (none: the reference has no scoring task)
  *   bs_forward_topk    <- (none: the reference's tail returns one token, decoding.cpp:24-66, never ranked candidates)
  *   bs_last_error      <- (none: the reference throws C++ exceptions across JNI,
@@ -322,6 +324,44 @@ typedef struct bs_ragged_step {
 } bs_ragged_step;
 int bs_forward_ragged(bs_stage *stage, const bs_ragged_step *step, const void *in, void *out,
                       float *logits, void *stream);
+
+/* ---- Tree verify pass: N draft-tree nodes per row in one pass over the weights (bf16 stages) ----
+ * Row b feeds N nodes of a tree whose root (node 0) is the row's last token; parents[b][i] < i names node i's parent.
+ *   in : first stage -> int32 ids [B][N]; otherwise fp32 hidden [B][N][hidden].
+ *   Node i is written to cache position past_b + i (the QKV epilogue of a seq = N pass) and attends every cached
+ *   position < past_b plus the pass's nodes that are i itself or an ancestor of i.  A cached key's ALiBi position is
+ *   its index, a node key's is past_b + depth(node).  A chain (parents[i] = i - 1) is a BS_STEP_VERIFY pass.
+ *   out / logits: as BS_STEP_VERIFY's -- the last stage writes the greedy id of every node, int32 [B][N] (never
+ *   screened), and with BS_STEP_LOGITS fp32 [B][N][vocab]; other stages write fp32 hidden [B][N][hidden].
+ *   A row with fewer real nodes is padded with extra children of the root: no other node can see them.
+ *   Device buffers replay a captured graph (the trees travel in a device table written ahead of the replay, so a
+ *   graph follows a new tree of the same (B, N)); BS_STEP_HOST_IO or bs_set_graphs(0) launch eagerly.  Results are
+ *   bit-identical from run to run.  The pass leaves the rows at past_b + N; the caller moves the accepted nodes' K / V
+ *   with bs_compact_kv and states the real position on its next call.
+ *   The first call allocates the tree table (and, if absent, the verify pass's buffers), counted under workspace_bytes.
+ *   A stage has ONE tree table: its tree passes must be issued on one stream (a pass on another stream could rewrite
+ *   the table before an earlier pass still queued has read it).
+ * BS_ERR_INVALID: N outside [2, 16], B * N > 32, past_b + N > max_ctx, parents[b][0] != -1 or parents[b][i] outside
+ *   [0, i), a flag other than BS_STEP_HOST_IO | BS_STEP_LOGITS, NULL arrays.
+ * BS_ERR_UNSUPPORTED: an fp32 stage, a BS_FLAG_INT8_KV stage, head_dim > 128 or head_dim % 8 != 0.
+ * BS_ERR_STATE: a classifier stage, a last stage without the whole lm_head, after bs_set_sampling chose top_k > 1, a
+ *   row that holds sampler, processor, guide or shared-prefix state. */
+typedef struct bs_tree_step {
+  int32_t batch;              /* B rows */
+  int32_t nodes;              /* N tree nodes per row, 2 <= N <= 16, B * N <= 32 */
+  int32_t slot;               /* first KV row */
+  int32_t flags;              /* BS_STEP_HOST_IO | BS_STEP_LOGITS */
+  const int32_t *past_lens;   /* host [B] */
+  const int32_t *parents;     /* host [B][N]: parents[b][0] = -1, 0 <= parents[b][i] < i otherwise */
+} bs_tree_step;
+int bs_forward_tree(bs_stage *stage, const bs_tree_step *step, const void *in, void *out, float *logits,
+                    void *stream);
+/* In-row KV compaction: in every layer of the stage, K and V, every head, position past + k of KV row `slot` receives
+ * what position past + src[k] held, k = 0 .. n - 1 (the accepted path of a tree pass becomes contiguous).  src is
+ * strictly increasing with src[k] >= k, n <= 16, past + src[n - 1] < max_ctx.  One launch, stream ordered, no
+ * synchronisation; exact.  n == 0 or src[k] == k for every k: BS_OK without a launch.
+ * BS_ERR_INVALID: bad indices.  BS_ERR_UNSUPPORTED: an fp32 stage, a BS_FLAG_INT8_KV stage. */
+int bs_compact_kv(bs_stage *stage, int32_t slot, int32_t past, const int32_t *src, int32_t n, void *stream);
 
 /* ---- Vocabulary-parallel head (stages with a head slice, or the last stage) ----
  * Argmax keys: uint64 (order(logit) << 32) | (0xFFFFFFFF - vocab_index), where order() maps
