@@ -17,7 +17,7 @@ LIB = os.path.join(PKG, "lib", "libbloomstage.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "head_score.hip", "attn_verify.hip", "attn_prefix.hip", "attn_ragged.hip", "attn_tree.hip", "row_sample.hip", "logit_proc.hip", "guide.hip", "kv_fork.hip", "beam_topk.hip", "stage.hip", "codec.cpp", "safetensors.cpp", "guide_table.cpp"]
+SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "head_score.hip", "attn_verify.hip", "attn_prefix.hip", "attn_ragged.hip", "attn_tree.hip", "row_sample.hip", "logit_proc.hip", "guide.hip", "kv_fork.hip", "beam_topk.hip", "lora.hip", "stage.hip", "codec.cpp", "safetensors.cpp", "guide_table.cpp"]
 # per-source extra flags: the prefill attention keeps its MFMA accumulators in VGPRs (attn_prefill.hip header); so does
 # the shared-prefix, the ragged and the tree attention, built without packed fp32 arithmetic (their per-chunk rescale
 # stays scalar VALU)

@@ -388,6 +388,37 @@ void launch_guide_advance_picks(const GuideBufs& gb, int slot, int B, const int*
 void launch_guide_advance(const GuideBufs& gb, int slot, const int* ids_host, const int* ids_dev, int n, hipStream_t s);
 int guide_advance_arg_ids();
 
+// ---- Per-row LoRA adapters (include/bloomstage.h "Per-row LoRA adapters"; lora.hip) ----
+constexpr int kLoraMax = 16;         // BS_LORA_MAX: adapters a stage holds at a time
+constexpr int kLoraMaxRank = 64;     // ranks are zero-padded to r_pad = 32 or 64
+constexpr int kLoraKSlice = 512;     // K elements one block of the shrink streams
+enum LoraTarget : int { LORA_QKV = 0, LORA_DENSE = 1, LORA_FC2 = 2, LORA_TARGETS = 3 };
+struct LoraDev {  // one entry of the device table [kLoraMax]; r_pad == 0: not loaded
+  const __bf16* a[LORA_TARGETS];  // [layers][r_pad][K_t] (lora_A, rank rows zero-padded); null: target not adapted
+  const __bf16* b[LORA_TARGETS];  // [layers][N_t][r_pad] (lora_B, rank columns zero-padded)
+  int r_pad;
+  float scale;
+};
+struct LoraBufs {
+  LoraDev* table;  // [kLoraMax]
+  int* rows;       // [max_batch] adapter id of each KV row, -1: none
+  float* u;        // [lora_ksplits(widest K)][max_tokens][kLoraMaxRank] the shrink's partials of one target
+};
+// Blocks the shrink spreads a K-wide reduction over: a function of K alone (static under graph capture).
+int lora_ksplits(int K);
+// table[id] = v / rows[slot .. slot + count) = id, stream ordered, by kernel arguments.
+void launch_lora_table(LoraDev* table, int id, const LoraDev& v, hipStream_t s);
+void launch_lora_rows(int* rows, int slot, int count, int id, hipStream_t s);
+// The update of one linear: for every token m of the B rows x S tokens whose KV row slot + b names an adapter with
+// this target (fixed_id >= 0: that adapter for every row), delta[m][n] = scale * sum_j B[n][j] * sum_k A[j][k] * x[m][k]
+// is added to what `ep` addresses -- EPI_RESID: out_f32[m][n] += delta; EPI_QKV: bf16(float(old) + delta) at the place
+// the GEMV epilogue routed column n to.  x bf16 [B * S][K]; K % 32 == 0, N % 16 == 0, head_dim % 4 == 0.  Two launches
+// on static grids (tiles = B * ceil(S / 16); shrink (tiles, lora_ksplits(K)), expand (tiles, ceil(N / 128))).
+void launch_lora_delta(const LoraBufs& lb, int fixed_id, int layer, int target, const void* x, int B, int S, int slot,
+                       int K, int N, const Epi& ep, hipStream_t s);
+// ctx bf16 [M][K] = merge of a deferred-merge decode attention's partials (what launch_linear_parts forms in LDS).
+void launch_lora_ctx_parts(const AttnParts& p, void* ctx_bf16, int M, int K, hipStream_t s);
+
 // ---- Weight-only int8 (bf16 stages with BS_FLAG_INT8_WEIGHTS; kernels.hip "Weight-only int8") ----
 // Q[n][k] = rne(W[n][k] / scale[n]), scale[n] = max_k |W[n][k]| / 127 (1 for a zero row); W bf16 [N][K].
 void launch_quantize_rows(const void* W_bf16, int8_t* Q, float* scale, int N, int K, hipStream_t s);

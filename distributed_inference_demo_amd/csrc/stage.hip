@@ -17,6 +17,7 @@
 //   head slices, sampling setters, the per-row sampler and verify-draw buffers, the graph cache
 //   forward_impl (checks, lazy buffers, capture or eager enqueue), bs_forward, bs_forward_score, bs_forward_topk
 //   bs_forward_ragged (rows of different lengths in one pass: attn_ragged.hip)
+//   per-row LoRA adapters (lora.hip): load / unload, the rows' adapter ids, bs_adapter_delta
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -110,9 +111,11 @@ struct GraphKey {
                    // of the key: the kernels read them from the device table
   int tree = 0;    // a tree pass (bs_forward_tree) of seq nodes per row; the trees are not part of the key: the
                    // attention reads them from the device table
+  int lora = 0;    // a row of the call names an adapter: the pass holds the LoRA launches; which adapter is not part of
+                   // the key: the kernels read both tables on the device
   bool operator==(const GraphKey& o) const {
     return B == o.B && seq == o.seq && slot == o.slot && flags == o.flags && tail == o.tail && prefix == o.prefix &&
-           tree == o.tree && in == o.in &&
+           tree == o.tree && lora == o.lora && in == o.in &&
            out == o.out && logits == o.logits && st == o.st && k == o.k && logprobs == o.logprobs && lse == o.lse;
   }
 };
@@ -331,6 +334,15 @@ struct bs_stage {
   TreeRow* tr_table = nullptr;         // [kTreeMaxRows]
   TreeRow* tr_host = nullptr;
   hipEvent_t tr_ev = nullptr;
+  // per-row LoRA adapters (lora.hip): the device table of kLoraMax adapters, the rows' adapter ids and the shrink's
+  // partials, one allocation made by the first bs_load_adapter (lr.table null: never); each adapter's arrays are one
+  // more allocation, counted as workspace until it is unloaded.  lr_ads mirrors the table (base null: not loaded) with
+  // the count of rows that name the adapter; lr_host mirrors the rows' ids for routing
+  LoraBufs lr{};
+  struct LoraHost { void* base = nullptr; LoraDev dev{}; int refs = 0; };
+  LoraHost lr_ads[kLoraMax];
+  std::vector<int> lr_host;  // [max_batch] adapter id, -1: none
+  int lr_active = 0;         // rows that name an adapter
 };
 
 // What a scoring pass (bs_forward_score) reads and writes instead of bs_forward's out / logits.
@@ -918,6 +930,14 @@ extern "C" int bs_reset_kv(bs_stage* s, int32_t slot) {
       s->px_host[i] = PrefixRow{0, 0};
     }
   }
+  if (s->lr_active) {  // so does the adapter it named
+    const int r0 = slot < 0 ? 0 : slot, n = slot < 0 ? s->d.max_batch : 1;
+    launch_lora_rows(s->lr.rows, r0, n, -1, s->own);
+    for (int i = r0; i < r0 + n; i++) {
+      if (s->lr_host[i] >= 0) { s->lr_ads[s->lr_host[i]].refs--; s->lr_active--; }
+      s->lr_host[i] = -1;
+    }
+  }
   HIP_TRY(hipStreamSynchronize(s->own));
   return BS_OK;
 }
@@ -1314,6 +1334,14 @@ static bool rows_guided(const bs_stage* s, int slot, int B) {
   return false;
 }
 
+// Does a row of [slot, slot + B) name an adapter (bs_set_row_adapter)?  Then the pass holds the LoRA launches.
+static bool rows_adapted(const bs_stage* s, int slot, int B) {
+  if (!s->lr_active) return false;
+  for (int b = 0; b < B; b++)
+    if (s->lr_host[slot + b] >= 0) return true;
+  return false;
+}
+
 // Does this step's attention take the shared-prefix route (attn_prefix.hip)?  A plain decode step of 2 .. 32 rows that
 // all hold the same declaration, each row at or beyond the shared positions.
 static bool prefix_route(const bs_stage* s, const bs_step* step, const std::vector<int>& pasts) {
@@ -1408,6 +1436,9 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
   const bool verify = (step->flags & BS_STEP_VERIFY) != 0;  // forward_impl checked the shape and the stage
   const int h = d.hidden, V = d.vocab, hd = s->hd, nh = d.n_head;
+  // a row of the call names an adapter: each of the QKV, dense and fc2 linears is followed by the two LoRA launches,
+  // a read-modify-write of what the base kernel just wrote (lora.hip); rows without an adapter leave them at once
+  const bool lora = rows_adapted(s, slot, B);
 
   // ---- input
   const float* cur = nullptr;
@@ -1460,6 +1491,12 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
     }
     if (!done)
       linear_ln(s, st, cur, 1, 0, w.t[T_LN1_G], w.t[T_LN1_B], wmat(w, T_QKV_W), M, 3 * h, h, with_splitk(s, e), 4);
+    if (lora) {
+      // the base path may have fused LN_in and left no bf16 copy: xn is free until fc1's LayerNorm.  The expand routes
+      // its columns by the epilogue the GEMV received, ahead of the attention launch
+      launch_ln_rows(cur, 1, 0, w.t[T_LN1_G], w.t[T_LN1_B], d.ln_eps, s->xn, M, h, st);
+      launch_lora_delta(s->lr, -1, l, LORA_QKV, s->xn, B, S, slot, h, 3 * h, e, st);
+    }
     // attention
     AttnArgs a{};
     a.q = s->q; a.k_cache = kbase; a.v_cache = kbase + s->kv_half; a.ctx_out = s->ctx; a.slopes = s->slopes;
@@ -1507,11 +1544,15 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
     }
     if (a.defer_merge) {
       const AttnParts parts{s->part_acc, s->part_ml, nsplit, nh, hd, s->max_chunks, slot};
-      ProfScope p(s, st, 1, gemv_bytes(s, dense, M, h, h, 4));
-      launch_wmat_parts(parts, dense, M, h, h, e2, st);
+      {
+        ProfScope p(s, st, 1, gemv_bytes(s, dense, M, h, h, 4));
+        launch_wmat_parts(parts, dense, M, h, h, e2, st);
+      }
+      if (lora) launch_lora_ctx_parts(parts, s->ctx, M, h, st);  // the merge the GEMV formed in LDS only
     } else {
       linear(s, st, s->ctx, dense, M, h, h, with_splitk(s, e2), 4);
     }
+    if (lora) launch_lora_delta(s->lr, -1, l, LORA_DENSE, s->ctx, B, S, slot, h, h, e2, st);
     // x2 = LN_post(a); g = gelu(x2 W1 + b1)
     Epi e3{};
     e3.kind = EPI_GELU; e3.bias = w.t[T_FC1_B]; e3.out_act = s->g; e3.ldo = 4 * h;
@@ -1522,6 +1563,7 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
     Epi e4{};
     e4.kind = EPI_RESID; e4.bias = w.t[T_FC2_B]; e4.out_f32 = nxt; e4.resid = s->attn; e4.ldo = h;
     linear(s, st, s->g, wmat(w, T_FC2_W), M, h, 4 * h, with_splitk(s, e4), 4);
+    if (lora) launch_lora_delta(s->lr, -1, l, LORA_FC2, s->g, B, S, slot, 4 * h, h, e4, st);
     cur = nxt;
   }
 
@@ -2350,6 +2392,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   GraphKey key{B, S, slot, step->flags, tail.kind, in, out, logits, st};
   key.prefix = shared ? 1 : 0;
   key.tree = tree ? 1 : 0;
+  key.lora = rows_adapted(s, slot, B) ? 1 : 0;
   if (tk) { key.out = tk->ids; key.logits = tk->logits; key.k = tk->k; key.logprobs = tk->logprobs; key.lse = tk->lse; }
   if (graph && !(exec = find_graph(s, key))) {
     hipGraph_t gr = nullptr;
@@ -2595,8 +2638,8 @@ extern "C" int bs_forward_ragged(bs_stage* s, const bs_ragged_step* step, const 
   for (int b = 0; b < B; b++) {
     const int slot = rows[b].slot;
     if (rows_sampled(s, slot, 1) || rows_processed(s, slot, 1) || rows_guided(s, slot, 1) ||
-        (s->px_active && s->px_host[slot].npos > 0))
-      return fail(BS_ERR_STATE, "bs_forward_ragged on a row that holds sampler, processor, guide or shared-prefix state");
+        (s->px_active && s->px_host[slot].npos > 0) || rows_adapted(s, slot, 1))
+      return fail(BS_ERR_STATE, "bs_forward_ragged on a row that holds sampler, processor, guide, shared-prefix or adapter state");
   }
   const bool host_io = (step->flags & BS_STEP_HOST_IO) != 0;
   const int M = (int)T, h = d.hidden, V = d.vocab, hd = s->hd, nh = d.n_head;
@@ -2711,5 +2754,182 @@ extern "C" int bs_forward_ragged(bs_stage* s, const bs_ragged_step* step, const 
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kernel launch: ") + hipGetErrorString(err));
   if (host_io) HIP_TRY(hipStreamSynchronize(st));
+  return BS_OK;
+}
+
+// ---- Per-row LoRA adapters (lora.hip).  The first load makes the device table of adapters (zeroed: nothing loaded),
+// the rows' ids (every row -1) and the shrink's partials; an adapter is one allocation holding, per target in its mask,
+// bf16 A [L][r_pad][K] and B [L][N][r_pad] with the rank zero-padded.  Setting a row is one small launch on the caller's
+// stream and a host mirror update; the captured graphs stay (whether a pass holds the LoRA launches is a bit of their
+// key, which adapter a row names is read on the device).
+static_assert(BS_LORA_MAX == kLoraMax && BS_LORA_QKV == 1 << LORA_QKV && BS_LORA_DENSE == 1 << LORA_DENSE &&
+                  BS_LORA_FC2 == 1 << LORA_FC2, "adapter constants");
+
+// K and N of target t's linear.
+static void lora_shape(const bs_stage* s, int t, int* K, int* N) {
+  const int h = s->d.hidden;
+  *K = t == LORA_FC2 ? 4 * h : h;
+  *N = t == LORA_QKV ? 3 * h : h;
+}
+
+static uint16_t lora_bf16(float f) {  // round to nearest even, as the weight upload does on the device
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);
+  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+static int lora_buffers(bs_stage* s) {
+  if (s->lr.table) return BS_OK;
+  const size_t mb = s->d.max_batch;
+  LoraBufs lr{};
+  Carver c;
+  c.piece(&lr.table, kLoraMax * sizeof(LoraDev));
+  c.piece(&lr.rows, mb * sizeof(int));
+  c.piece(&lr.u, (size_t)lora_ksplits(4 * s->d.hidden) * s->d.max_tokens * kLoraMaxRank * 4);
+  const int ar = c.alloc(s->own);
+  if (ar == Carver::NO_MEMORY) return fail(BS_ERR_OOM, "adapter table allocation failed (" + std::to_string(c.total) + " B)");
+  if (ar == Carver::NOT_ZEROED) return fail(BS_ERR_DEVICE, "adapter table memset");
+  launch_lora_rows(lr.rows, 0, (int)mb, -1, s->own);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->own) != hipSuccess) {
+    hipFree(c.base);
+    return fail(BS_ERR_DEVICE, "adapter row table clear");
+  }
+  s->owned.push_back({c.base, c.total});
+  s->lr = lr;
+  s->lr_host.assign(mb, -1);
+  return BS_OK;
+}
+
+extern "C" int bs_load_adapter(bs_stage* s, const bs_adapter_desc* ad, int32_t* adapter_id) {
+  if (!s || !ad || !adapter_id) return fail(BS_ERR_INVALID, "stage/adapter/adapter_id is NULL");
+  if (!s->bf16) return fail(BS_ERR_UNSUPPORTED, "adapters need a BFLOAT16 stage (the kernels are bf16 MFMA)");
+  if (s->d.hidden % 32 || s->hd % 4) return fail(BS_ERR_UNSUPPORTED, "adapters need hidden % 32 == 0 and head_dim % 4 == 0");
+  if (ad->rank < 1 || ad->rank > kLoraMaxRank) return fail(BS_ERR_INVALID, "adapter rank outside [1, 64]");
+  const int all = BS_LORA_QKV | BS_LORA_DENSE | BS_LORA_FC2;
+  if (!ad->targets || (ad->targets & ~all)) return fail(BS_ERR_INVALID, "adapter targets: a non-empty mask of BS_LORA_*");
+  if (!std::isfinite(ad->scale)) return fail(BS_ERR_INVALID, "adapter scale is not finite");
+  for (int t = 0; t < LORA_TARGETS; t++)
+    if ((ad->targets >> t & 1) && (!ad->a[t] || !ad->b[t])) return fail(BS_ERR_INVALID, "adapter arrays of a target in the mask are NULL");
+  if (s->L <= 0) return fail(BS_ERR_INVALID, "the stage holds no layers to adapt");
+  int id = 0;
+  while (id < kLoraMax && s->lr_ads[id].base) id++;
+  if (id == kLoraMax) return fail(BS_ERR_STATE, "the stage holds BS_LORA_MAX adapters already");
+  HIP_TRY(hipSetDevice(s->d.device));
+  int rc = lora_buffers(s);
+  if (rc != BS_OK) return rc;
+  const int r = ad->rank, rp = r <= 32 ? 32 : 64;
+  const size_t L = s->L;
+  uint16_t *pa[LORA_TARGETS] = {}, *pb[LORA_TARGETS] = {};
+  Carver c;
+  for (int t = 0; t < LORA_TARGETS; t++) {
+    if (!(ad->targets >> t & 1)) continue;
+    int K, N;
+    lora_shape(s, t, &K, &N);
+    c.piece(&pa[t], L * rp * K * 2);
+    c.piece(&pb[t], L * N * rp * 2);
+  }
+  if (c.alloc() != Carver::OK) return fail(BS_ERR_OOM, "adapter allocation failed (" + std::to_string(c.total) + " B)");
+  LoraDev dev{};
+  dev.r_pad = rp;
+  dev.scale = ad->scale;
+  std::vector<uint16_t> img;
+  hipError_t e = hipSuccess;
+  for (int t = 0; t < LORA_TARGETS && e == hipSuccess; t++) {
+    if (!pa[t]) continue;
+    int K, N;
+    lora_shape(s, t, &K, &N);
+    img.assign(L * rp * K, 0);  // A: rank rows r .. rp - 1 stay zero
+    for (size_t l = 0; l < L; l++)
+      for (int j = 0; j < r; j++)
+        for (int k = 0; k < K; k++) img[(l * rp + j) * K + k] = lora_bf16(ad->a[t][(l * r + j) * K + k]);
+    e = hipMemcpy(pa[t], img.data(), img.size() * 2, hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    img.assign(L * N * rp, 0);  // B: rank columns r .. rp - 1 stay zero
+    for (size_t ln = 0; ln < L * N; ln++)
+      for (int j = 0; j < r; j++) img[ln * rp + j] = lora_bf16(ad->b[t][ln * r + j]);
+    e = hipMemcpy(pb[t], img.data(), img.size() * 2, hipMemcpyHostToDevice);
+    dev.a[t] = (const __bf16*)pa[t];
+    dev.b[t] = (const __bf16*)pb[t];
+  }
+  if (e == hipSuccess) {  // last: the arrays are in place
+    launch_lora_table(s->lr.table, id, dev, s->own);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s->own);
+  }
+  if (e != hipSuccess) {
+    hipFree(c.base);
+    return fail(BS_ERR_DEVICE, std::string("adapter copy: ") + hipGetErrorString(e));
+  }
+  s->owned.push_back({c.base, c.total});
+  s->lr_ads[id].base = c.base;
+  s->lr_ads[id].dev = dev;
+  s->lr_ads[id].refs = 0;
+  *adapter_id = id;
+  return BS_OK;
+}
+
+extern "C" int bs_unload_adapter(bs_stage* s, int32_t id) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (id < 0 || id >= kLoraMax || !s->lr_ads[id].base) return fail(BS_ERR_INVALID, "no such adapter is loaded");
+  if (s->lr_ads[id].refs) return fail(BS_ERR_STATE, "a row still names the adapter (bs_set_row_adapter with -1 clears it)");
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());  // launches that read the adapter have finished
+  launch_lora_table(s->lr.table, id, LoraDev{}, s->own);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->own));
+  void* base = s->lr_ads[id].base;
+  s->owned.erase(std::find_if(s->owned.begin(), s->owned.end(), [&](const OwnedAlloc& a) { return a.p == base; }));
+  s->lr_ads[id] = bs_stage::LoraHost{};
+  HIP_TRY(hipFree(base));
+  return BS_OK;
+}
+
+extern "C" int bs_set_row_adapter(bs_stage* s, int32_t slot, int32_t count, int32_t id, void* stream) {
+  if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
+  if (count <= 0 || slot < 0 || slot > s->d.max_batch - count) return fail(BS_ERR_INVALID, "slot range outside max_batch");
+  if (id < -1 || id >= kLoraMax || (id >= 0 && !s->lr_ads[id].base)) return fail(BS_ERR_INVALID, "no such adapter is loaded");
+  if (!s->lr.table) return BS_OK;  // nothing was ever loaded: id is -1
+  HIP_TRY(hipSetDevice(s->d.device));
+  launch_lora_rows(s->lr.rows, slot, count, id, stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("adapter row table: ") + hipGetErrorString(err));
+  for (int i = slot; i < slot + count; i++) {
+    int& cur = s->lr_host[i];
+    if (cur >= 0) { s->lr_ads[cur].refs--; s->lr_active--; }
+    cur = id;
+    if (id >= 0) { s->lr_ads[id].refs++; s->lr_active++; }
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_read_row_adapter(bs_stage* s, int32_t slot, int32_t* id) {
+  if (!s || !id) return fail(BS_ERR_INVALID, "stage/adapter_id is NULL");
+  if (slot < 0 || slot >= s->d.max_batch) return fail(BS_ERR_INVALID, "slot out of range");
+  *id = -1;
+  if (!s->lr.table) return BS_OK;
+  HIP_TRY(hipSetDevice(s->d.device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(id, s->lr.rows + slot, 4, hipMemcpyDeviceToHost));
+  return BS_OK;
+}
+
+extern "C" int bs_adapter_delta(bs_stage* s, int32_t id, int32_t layer, int32_t target, const void* x, int32_t batch,
+                                int32_t seq, float* out, void* stream) {
+  if (!s || !x || !out) return fail(BS_ERR_INVALID, "stage/x/out is NULL");
+  if (id < 0 || id >= kLoraMax || !s->lr_ads[id].base) return fail(BS_ERR_INVALID, "no such adapter is loaded");
+  if (layer < 0 || layer >= s->L) return fail(BS_ERR_INVALID, "layer outside the stage");
+  const int t = target == BS_LORA_QKV ? LORA_QKV : target == BS_LORA_DENSE ? LORA_DENSE : target == BS_LORA_FC2 ? LORA_FC2 : -1;
+  if (t < 0 || !s->lr_ads[id].dev.a[t]) return fail(BS_ERR_INVALID, "target: one BS_LORA_* bit the adapter holds");
+  if (batch <= 0 || seq <= 0 || (long)batch * seq > s->d.max_tokens) return fail(BS_ERR_INVALID, "batch * seq outside [1, max_tokens]");
+  if ((uintptr_t)x & 15) return fail(BS_ERR_INVALID, "x must be 16-byte aligned");
+  int K, N;
+  lora_shape(s, t, &K, &N);
+  HIP_TRY(hipSetDevice(s->d.device));
+  Epi e{};
+  e.kind = EPI_RESID; e.out_f32 = out; e.ldo = N;
+  launch_lora_delta(s->lr, id, layer, t, x, batch, seq, 0, K, N, e, stream ? (hipStream_t)stream : s->own);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("adapter delta: ") + hipGetErrorString(err));
   return BS_OK;
 }

@@ -88,6 +88,13 @@ each row at its own length, the stage's weights streamed once for the wave inste
 sample's first token comes from it.  Plain greedy generation on one rank with the HIP stage, bf16, kv bf16: not with
 --sample, the logit processor or guide options, --shared-prefix, --speculate, --sample-speculate, --num-beams, --score,
 --kv int8 or --prefill 0.  Same tokens as without the option up to bf16 rounding of the attention context.
+--adapters N --adapter-rank R [--adapter-seed S] [--adapter-amplitude A] (opt-in) is per-row LoRA serving on one GPU with the
+HIP stage: N synthetic adapters of rank R on query_key_value, dense and dense_4h_to_h are loaded once (bs_load_adapter);
+sample i names adapter i % (N + 1) - 1 (every (N + 1)-th sample runs the base model), set at admission beside the
+sampler / processor / guide calls (bs_set_row_adapter) and cleared when its row retires, so one stage and one copy of
+the weights serve every variant in the same decode steps.  Combines with --sample, the logit processor and guide
+options, --kv int8 and int8 / MXFP4 weights; not with --ragged-admission (the ragged pass applies no adapter),
+--shared-prefix (a forked prefix would hold the base model's K / V), speculation, --num-beams, --score or --prefill 0.
 Differences from the reference, by design: full-context decode (the reference
 header feeds only the last token), argmax (or, with --sample, seeded per-request top-k / top-p sampling) instead of
 unseeded top-k, token ids in (no tokenizer).
@@ -151,6 +158,10 @@ class RunConfig:
     choice: tuple = ()                # guided decoding: token-id sequences ("ID,ID,..." or lists), one is generated, then eos_id
     ragged_admission: bool = False    # the samples admitted in one round are prefilled by one ragged pass (one rank, greedy)
     speculate_tree: int = 0           # tree speculative decoding: nodes per tree pass, 2..16 (0 = off; one GPU, draft ngram)
+    adapters: int = 0                 # per-row LoRA: N synthetic adapters; sample i runs adapter i % (N + 1) - 1 (-1: the base model)
+    adapter_rank: int = 16            # per-row LoRA: rank of the synthetic adapters (1..64)
+    adapter_seed: int = 0             # per-row LoRA: adapter k is lora.synthetic(adapter_seed + k, ...)
+    adapter_amplitude: float = 1.0    # per-row LoRA: lora.synthetic's amplitude, the size of a linear's update per element
 
     @property
     def guided(self):
@@ -173,7 +184,30 @@ class RunConfig:
                 "min_new_tokens": self.min_new_tokens, "eos_id": self.eos_id if self.min_new_tokens else -1,
                 "bias": list(self.token_bias), "bad_tokens": list(self.bad_token)}
 
+    def make_adapters(self, hidden, layers):
+        """The run's synthetic adapters on query_key_value, dense and dense_4h_to_h of `layers` layers."""
+        from . import lora
+        return [lora.synthetic(self.adapter_seed + k, self.adapter_rank, lora.TARGETS, hidden, layers,
+                               self.adapter_amplitude)
+                for k in range(self.adapters)]
+
     def __post_init__(self):
+        if self.adapters:
+            if not 1 <= self.adapters <= 16 or not 1 <= self.adapter_rank <= 64:
+                raise ValueError(f"adapters must be in [0, 16] and adapter_rank in [1, 64] (got {self.adapters}, "
+                                 f"{self.adapter_rank}): a stage holds 16 adapters of rank <= 64")
+            if self.ragged_admission:
+                raise ValueError("adapters and ragged_admission exclude each other: the ragged prefill pass applies no "
+                                 "adapter (bs_forward_ragged rejects a row that names one)")
+            bad = [name for name, on in (
+                ("speculate", self.speculate), ("sample_speculate", self.sample_speculate),
+                ("speculate_tree", self.speculate_tree), ("num_beams", self.num_beams), ("score", self.score),
+                ("max_length == 0", self.max_length <= 0), ("prefill = False", not self.prefill),
+                ("shared_prefix (a forked prefix would hold the base model's K / V)", self.shared_prefix),
+                ("dtype != 'bf16'", self.dtype != "bf16")) if on]
+            if bad:
+                raise ValueError("adapters is plain generation with admission prefills on a bf16 stage: it excludes "
+                                 + ", ".join(bad))
         if self.shared_prefix < 0:
             raise ValueError(f"shared_prefix must be >= 0 (got {self.shared_prefix})")
         if self.ragged_admission:
@@ -342,6 +376,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
         raise ValueError("sample is the HIP stage's per-row sampler: not available with an executor_factory")
     if cfg.ragged_admission and (world != 1 or executor_factory is not None):
         raise ValueError("ragged_admission runs on one rank (world == 1) with the HIP stage: no executor_factory")
+    if cfg.adapters and (world != 1 or executor_factory is not None):
+        raise ValueError("adapters runs on one rank (world == 1) with the HIP stage: no executor_factory")
     proc = cfg.processors
     if proc and executor_factory is not None:
         raise ValueError("the logit processors are the HIP stage's: not available with an executor_factory")
@@ -440,6 +476,12 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
                                 kv_int8=cfg.kv == "int8", sample=cfg.sample or bool(proc) or cfg.guided,
                                 extra_rows=int(fork))
     guide_id = pipe.load_guide(guide) if guide is not None else None  # once, outside the decode loop (last rank)
+    # per-row LoRA: the adapters are loaded once; sample i names adapter i % (N + 1) - 1 from its admission to its
+    # last decode round (every (N + 1)-th sample runs the base model)
+    adapter_ids = [pipe.ex.stage.load_adapter(a) for a in cfg.make_adapters(model.hidden, le - lb)] if cfg.adapters else []
+
+    def row_adapter(r, k):
+        pipe.ex._run(lambda h: pipe.ex.stage.set_row_adapter(r, adapter_ids[k] if k >= 0 else -1, stream=h), ())
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "rounds": T, "prefill": pf,
                     **({"shared_prefix": P, "prefix_fork": fork} if P else {})})
@@ -472,6 +514,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     for t in range(T + 1):
         for r in release[t] if (fork and cfg.prefix_attention) else ():  # an idle row stands at position 0
             pipe.set_row_prefix(r // mb, r % mb, 0, 0)
+        for r in release[t] if adapter_ids else ():
+            row_adapter(r, -1)
         if cfg.ragged_admission and admit[t]:  # the round's wave as one ragged pass, each row from an empty KV row
             wave = admit[t]
             toks = pipe.prefill_rows([r for _, r in wave], torch.cat([pids[i].view(-1) for i, _ in wave]),
@@ -480,6 +524,8 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
             for k, (i, _) in enumerate(wave):
                 first[i] = toks[k:k + 1]
         for i, r in admit[t] if (pf and not cfg.ragged_admission) else ():
+            if adapter_ids:  # the request's adapter, ordered before every pass of its row
+                row_adapter(r, i % (cfg.adapters + 1) - 1)
             if sampling:  # the row's sampler for this request, ordered before its prefill pass (last rank)
                 pipe.set_row_sampler(r // mb, r % mb, seed=request_seed(cfg.sample_seed, i), **sampling)
             if fork:
@@ -532,6 +578,9 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
         res.update(ragged_admission=True, prefill_passes=sum(1 for a in admit if a), prefill_tokens=prefill_tokens)
     if sampling:
         res.update(sample=True, sample_seed=cfg.sample_seed, **sampling)
+    if adapter_ids:
+        res.update(adapters=cfg.adapters, adapter_rank=cfg.adapter_rank, adapter_seed=cfg.adapter_seed,
+                   sample_adapters=[i % (cfg.adapters + 1) - 1 for i in range(cfg.num_sample)])
     if proc:
         res.update(processors={k: v for k, v in proc.items() if k not in ("bias", "bad_tokens")},
                    token_bias=[list(e) for e in cfg.token_bias], bad_token=list(cfg.bad_token))

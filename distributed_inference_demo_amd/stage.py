@@ -45,6 +45,8 @@ BS_NOTE_GENERATED = 16    # bs_note_tokens flags: the noted tokens also count as
 BS_ROW_BIAS_MAX = 64
 BS_GUIDE_MAX = 16         # guides a stage holds at a time
 BS_GUIDE_SLICE = 4096     # vocabulary entries one block of the guide apply kernel owns
+BS_LORA_MAX = 16          # adapters a stage holds at a time
+BS_LORA_QKV, BS_LORA_DENSE, BS_LORA_FC2 = 1, 2, 4  # bs_adapter_desc.targets
 BS_FLAG_INT8_WEIGHTS = 1  # bs_stage_desc.flags: weight-only int8 block matrices
 BS_FLAG_CLASSIFIER = 2    # bs_stage_desc.flags: sequence-classification tail (score head, class ids out)
 BS_FLAG_INT8_KV = 4       # bs_stage_desc.flags: int8 KV cache, one fp32 scale per (position, head) vector
@@ -115,6 +117,12 @@ class GuideDesc(ctypes.Structure):
                 ("edge_next", ctypes.POINTER(ctypes.c_int32)), ("default_next", ctypes.POINTER(ctypes.c_int32))]
 
 
+class AdapterDesc(ctypes.Structure):
+    """bs_adapter_desc: a LoRA adapter's host arrays, index 0 / 1 / 2 = qkv / dense / fc2."""
+    _fields_ = [("rank", ctypes.c_int32), ("scale", ctypes.c_float), ("targets", ctypes.c_int32),
+                ("a", ctypes.c_void_p * 3), ("b", ctypes.c_void_p * 3)]
+
+
 class RowDraw(ctypes.Structure):
     """bs_row_draw: read-out of a row's last draw."""
     _fields_ = [("threshold", ctypes.c_float), ("n_nucleus", ctypes.c_int32), ("n_candidates", ctypes.c_int32),
@@ -139,6 +147,7 @@ EXPORTS = [
     "bs_set_row_processor", "bs_note_tokens", "bs_process_logits", "bs_read_row_tokens",
     "bs_load_guide", "bs_unload_guide", "bs_set_row_guide", "bs_advance_row_guide", "bs_guide_logits",
     "bs_read_row_guide", "bs_forward_ragged", "bs_forward_tree", "bs_compact_kv",
+    "bs_load_adapter", "bs_unload_adapter", "bs_set_row_adapter", "bs_read_row_adapter", "bs_adapter_delta",
 ]
 
 _LIB = None
@@ -213,6 +222,11 @@ def lib():
         L.bs_advance_row_guide.argtypes = [vp, i32, vp, i32, i32, vp]
         L.bs_guide_logits.argtypes = [vp, i32, i32, vp, i32, i32, vp]
         L.bs_read_row_guide.argtypes = [vp, i32] + [ctypes.POINTER(i32)] * 4
+        L.bs_load_adapter.argtypes = [vp, ctypes.POINTER(AdapterDesc), ctypes.POINTER(i32)]
+        L.bs_unload_adapter.argtypes = [vp, i32]
+        L.bs_set_row_adapter.argtypes = [vp, i32, i32, i32, vp]
+        L.bs_read_row_adapter.argtypes = [vp, i32, ctypes.POINTER(i32)]
+        L.bs_adapter_delta.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp]
         L.bs_set_graphs.argtypes = [vp, i32]
         L.bs_set_head_screen.argtypes = [vp, i32]
         L.bs_read_head_screen.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(i32)]
@@ -697,6 +711,46 @@ class Stage:
         v = [ctypes.c_int32() for _ in range(4)]
         _check(lib().bs_read_row_guide(self._h, int(slot), *[ctypes.byref(x) for x in v]))
         return dict(zip(("guide", "state", "n_steps", "n_rejected"), (x.value for x in v)))
+
+    # ---- per-row LoRA adapters (bs_load_adapter; bf16 stages)
+    def load_adapter(self, adapter):
+        """bs_load_adapter: copy a lora.Adapter (rank, scale, a / b: dicts of "qkv" / "dense" / "fc2" to fp32 arrays
+        [layers][rank][K] / [layers][N][rank] for the stage's local layers) to the device and return its id.  May
+        synchronise."""
+        d = AdapterDesc(int(adapter.rank), float(adapter.scale), 0)
+        keep = []
+        for t, name in enumerate(("qkv", "dense", "fc2")):
+            if name in adapter.a:
+                a = np.ascontiguousarray(adapter.a[name], dtype=np.float32)
+                b = np.ascontiguousarray(adapter.b[name], dtype=np.float32)
+                keep += [a, b]
+                d.targets |= 1 << t
+                d.a[t], d.b[t] = a.ctypes.data, b.ctypes.data
+        aid = ctypes.c_int32(-1)
+        _check(lib().bs_load_adapter(self._h, ctypes.byref(d), ctypes.byref(aid)))
+        return aid.value
+
+    def unload_adapter(self, adapter_id):
+        """bs_unload_adapter: free an adapter no row names.  Synchronises."""
+        _check(lib().bs_unload_adapter(self._h, int(adapter_id)))
+
+    def set_row_adapter(self, slot, adapter_id, count=1, stream=None):
+        """bs_set_row_adapter: KV rows [slot, slot + count) name the adapter from here on (-1: none).  Stream ordered;
+        captured decode graphs stay and follow the change."""
+        _check(lib().bs_set_row_adapter(self._h, int(slot), int(count), int(adapter_id), stream))
+
+    def read_row_adapter(self, slot):
+        """bs_read_row_adapter: the adapter id row `slot` names on the device (-1: none).  Synchronises."""
+        aid = ctypes.c_int32(-1)
+        _check(lib().bs_read_row_adapter(self._h, int(slot), ctypes.byref(aid)))
+        return aid.value
+
+    def adapter_delta(self, adapter_id, layer, target, x, out, batch, seq, stream=None):
+        """bs_adapter_delta: out fp32 [batch * seq][N] += scale * B (A x) for device activations x bf16 [batch * seq][K]
+        of local layer `layer` and one target (a BS_LORA_* bit), every row with `adapter_id`.  Stream ordered."""
+        _check(lib().bs_adapter_delta(self._h, int(adapter_id), int(layer), int(target), _ptr(x), int(batch), int(seq),
+                                      _ptr(out), stream))
+        return out
 
     def set_graphs(self, on=True):
         """bs_set_graphs: replay captured decode graphs (default) or launch every step eagerly."""

@@ -314,7 +314,7 @@ int bs_forward_topk(bs_stage *stage, const bs_step *step, const void *in, int32_
  *   past_b + S_b > max_ctx, T > max_tokens, a slot outside max_batch or named twice, logits wanted on a non-last stage.
  * BS_ERR_UNSUPPORTED: an fp32 stage, a BS_FLAG_INT8_KV stage, head_dim > 128.
  * BS_ERR_STATE: a classifier stage, after bs_set_sampling chose top_k > 1, a last stage without the whole lm_head, a
- *   row that holds sampler, processor, guide or shared-prefix state. */
+ *   row that holds sampler, processor, guide or shared-prefix state, a row that names an adapter (bs_set_row_adapter). */
 typedef struct bs_ragged_step {
   int32_t rows;               /* B >= 1 */
   int32_t flags;              /* BS_STEP_HOST_IO | BS_STEP_LOGITS */
@@ -615,6 +615,63 @@ int bs_guide_logits(bs_stage *stage, int32_t slot, int32_t batch, float *logits,
 int bs_read_row_guide(bs_stage *stage, int32_t slot, int32_t *guide_id, int32_t *state, int32_t *n_steps,
                       int32_t *n_rejected);
 
+/* ---- Per-row LoRA adapters (bf16 stages) ----
+ * A stage may hold up to BS_LORA_MAX low-rank adapters on the device, and every KV row may name one of them.  Every
+ * pass that goes through bs_forward, bs_forward_score, bs_forward_topk or bs_forward_tree (plain, verify, the
+ * shared-prefix route included) then computes, for the rows that name an adapter a and for each adapted linear,
+ *   y = W x + b + scale_a * B_a (A_a x)
+ * next to the unchanged base product, so the update also works on BS_FLAG_INT8_WEIGHTS / BS_FLAG_MXFP4_WEIGHTS stages
+ * (LoRA over a quantised base) and on a BS_FLAG_INT8_KV cache.  Targets: query_key_value, self_attention.dense and
+ * dense_4h_to_h; dense_h_to_4h (a GELU follows it) and the lm_head are not adaptable.  A row without an adapter, in
+ * the same pass, gets the bits of a stage that never loaded one; a stage that never loads one allocates and launches
+ * nothing new.
+ *   Arithmetic: A and B are rounded to bf16 on upload; x is the linear's bf16 input; u = A x and B u accumulate in
+ *   fp32, scale * u enters the second product as a bf16 pair hi + lo.  dense / fc2: the fp32 output of the base kernel
+ *   gets the update added.  query_key_value: q and the new K / V rows were stored as bf16 by the base kernel and are
+ *   re-stored as bf16(float(old) + update) before the attention runs: against a merged weight matrix one more bf16
+ *   rounding, at most one bf16 ulp.  Results are bit-identical from run to run and between graph replay and eager
+ *   launches.
+ * bs_forward_ragged on a row that names an adapter is BS_ERR_STATE. */
+#define BS_LORA_MAX 16
+#define BS_LORA_QKV 1    /* self_attention.query_key_value: K = hidden, N = 3 * hidden */
+#define BS_LORA_DENSE 2  /* self_attention.dense:           K = hidden, N = hidden */
+#define BS_LORA_FC2 4    /* mlp.dense_4h_to_h:              K = 4 * hidden, N = hidden */
+typedef struct bs_adapter_desc {
+  int32_t rank;     /* 1 .. 64; zero-padded to 32 or 64 on the device */
+  float scale;      /* lora_alpha / rank (finite) */
+  int32_t targets;  /* a non-empty mask of BS_LORA_* */
+  /* Index 0 / 1 / 2 = BS_LORA_QKV / BS_LORA_DENSE / BS_LORA_FC2; read for the targets in the mask only.  Host fp32 in
+   * HF / PEFT orientation for the stage's local layers: a = lora_A.weight [layers][rank][K], b = lora_B.weight
+   * [layers][N][rank]. */
+  const float *a[3];
+  const float *b[3];
+} bs_adapter_desc;
+/* Copy an adapter to the device and return its id in *adapter_id (0 .. BS_LORA_MAX - 1).  May synchronise: meant to
+ * run outside the decode loop.  The kernels read adapters through a fixed device table, so loading and unloading keep
+ * every captured graph.  The first load also makes that table, the rows' adapter ids and the partials of the first
+ * product (hidden-width-dependent splits x max_tokens x 64 floats); an adapter is one more allocation; all of it is
+ * counted under workspace_bytes.  BS_ERR_UNSUPPORTED: an fp32 stage, hidden % 32 != 0 or head_dim % 4 != 0.
+ * BS_ERR_INVALID: rank outside [1, 64], an empty or unknown target mask, a non-finite scale, a NULL array of a target
+ * in the mask, a stage without layers.  BS_ERR_STATE: a 17th adapter. */
+int bs_load_adapter(bs_stage *stage, const bs_adapter_desc *adapter, int32_t *adapter_id);
+/* Free an adapter.  Synchronises the device.  BS_ERR_INVALID: an id that is not loaded.  BS_ERR_STATE: a row still names
+ * it (bs_set_row_adapter with -1, or bs_reset_kv, clears a row). */
+int bs_unload_adapter(bs_stage *stage, int32_t adapter_id);
+/* KV rows [slot, slot + count) name adapter `adapter_id` (-1: none) from here on, ordered on `stream` (NULL = the
+ * stage's own) like a forward; no synchronisation, no allocation, captured graphs stay (a replayed step follows the
+ * table).  bs_reset_kv clears the rows it resets.  BS_ERR_INVALID: a bad row range, an id that is not loaded. */
+int bs_set_row_adapter(bs_stage *stage, int32_t slot, int32_t count, int32_t adapter_id, void *stream);
+/* The adapter id row `slot` names on the device (-1: none).  Synchronises the device. */
+int bs_read_row_adapter(bs_stage *stage, int32_t slot, int32_t *adapter_id);
+/* Run the two kernels of a pass -- for verification and for callers that own the base product -- on device
+ * activations x bf16 [batch * seq][K] (16-byte aligned) of local layer `layer` and ONE target (a BS_LORA_* bit the
+ * adapter holds): out fp32 [batch * seq][N] += scale * B (A x), every row with `adapter_id`.  Tokens are tiled as a
+ * pass tiles them (16 consecutive tokens of one row).  Stream ordered; uses the stage's partials buffer, so it is
+ * ordered with the stage's forwards like any call (one stage is single-producer).  batch * seq <= max_tokens.
+ * BS_ERR_INVALID: bad id, layer, target or shape, NULL pointers. */
+int bs_adapter_delta(bs_stage *stage, int32_t adapter_id, int32_t layer, int32_t target, const void *x_bf16_dev,
+                     int32_t batch, int32_t seq, float *out_dev, void *stream);
+
 /* Decode steps (S = 1) and BS_STEP_VERIFY passes on device buffers are captured once per shape into a hipGraph and replayed
  * (the default, on = 1); on = 0 launches them eagerly every step (same kernels, same results: for
  * debugging and A/B timing).  Drops captured graphs.  Returns BS_OK.  A stage starts with graphs off
@@ -639,7 +696,7 @@ int bs_set_head_screen(bs_stage *stage, int32_t on);
 int bs_read_head_screen(bs_stage *stage, int32_t row, float *hilo, float *lstar, int32_t *list, int32_t *count);
 
 /* Forget the cached positions of one KV row (slot), or of all rows when slot < 0, and the rows' shared-prefix
- * declarations (bs_set_row_prefix). */
+ * declarations (bs_set_row_prefix) and adapter ids (bs_set_row_adapter). */
 int bs_reset_kv(bs_stage *stage, int32_t slot);
 /* Read back KV row `slot` of the stage's local layer `layer`, positions [pos0, pos0 + npos), as fp32
  * out[2 (K, V)][n_head][npos][head_dim].  Synchronizes the stage's own stream; the caller orders any
