@@ -17,14 +17,14 @@ LIB = os.path.join(PKG, "lib", "libbloomstage.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "head_score.hip", "attn_verify.hip", "attn_prefix.hip", "attn_ragged.hip", "attn_tree.hip", "row_sample.hip", "logit_proc.hip", "guide.hip", "kv_fork.hip", "beam_topk.hip", "lora.hip", "stage.hip", "codec.cpp", "safetensors.cpp", "guide_table.cpp"]
+SOURCES = ["kernels.hip", "attn_prefill.hip", "kv_int8.hip", "kv_mxfp4.hip", "head_score.hip", "attn_verify.hip", "attn_prefix.hip", "attn_ragged.hip", "attn_tree.hip", "row_sample.hip", "logit_proc.hip", "guide.hip", "kv_fork.hip", "beam_topk.hip", "lora.hip", "stage.hip", "codec.cpp", "safetensors.cpp", "guide_table.cpp"]
 # per-source extra flags: the prefill attention keeps its MFMA accumulators in VGPRs (attn_prefill.hip header); so does
 # the shared-prefix, the ragged and the tree attention, built without packed fp32 arithmetic (their per-chunk rescale
 # stays scalar VALU)
 _VGPR_NO_PK = ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA = {"attn_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          "attn_prefix.hip": _VGPR_NO_PK, "attn_ragged.hip": _VGPR_NO_PK, "attn_tree.hip": _VGPR_NO_PK}
-HEADERS = ["common.h", "kernels.h", "attn_merge.h", "safetensors.h", "stage_weights.h", "guide_table.h"]
+HEADERS = ["common.h", "kernels.h", "attn_merge.h", "mx4.h", "safetensors.h", "stage_weights.h", "guide_table.h"]
 STAMP = os.path.join(OBJ, "build_id")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-result", "-Wno-unused-value", f"-I{os.path.join(ROOT, 'include')}"]

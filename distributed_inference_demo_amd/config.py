@@ -53,9 +53,11 @@ def get(name: str) -> BloomDims:
 MXFP4_BYTES_PER_WEIGHT = 0.5 + 1.0 / 32
 
 
-def kv_bytes_per_element(m: BloomDims, kv_int8: bool = False) -> float:
+def kv_bytes_per_element(m: BloomDims, kv_int8: bool = False, *, kv_mxfp4: bool = False) -> float:
     """HBM bytes per cached K/V element: 2 (bf16), or 1 + 4 / head_dim for the int8 cache (one int8 code per element
     and one fp32 scale per (position, head) vector, BS_FLAG_INT8_KV).  Feeds decode_step_bytes' kv_bytes."""
+    if kv_mxfp4:  # BS_FLAG_MXFP4_KV: a 4-bit code per element and one E8M0 byte per 32
+        return 0.5 + 1.0 / 32
     return 1.0 + 4.0 / m.head_dim if kv_int8 else 2.0
 
 

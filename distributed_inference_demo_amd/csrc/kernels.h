@@ -201,10 +201,27 @@ void launch_kv_dequant(const void* k_codes, const void* v_codes, const KvQ8& kq,
 void launch_kv_quant(void* k_codes, void* v_codes, const KvQ8& kq, const int* past_dev, int B, int S, int slot,
                      int n_head, int head_dim, int max_ctx, int lmax, hipStream_t s);
 
+// ---- MXFP4 KV cache (bf16 stages with BS_FLAG_MXFP4_KV; kv_mxfp4.hip) ----
+// The E8M0 bytes beside the E2M1 codes of one layer ([max_batch][heads][max_ctx][hd / 32], K and V; the codes are
+// [max_batch][heads][max_ctx][hd / 2] bytes), and the int8 cache's bf16 staging buffers.  head_dim % 32 == 0.
+struct KvMx4 {
+  uint8_t* k_scale;
+  uint8_t* v_scale;
+  __bf16* k_stage;
+  __bf16* v_stage;
+};
+// The three launches of the int8 cache, same call sites and contracts; the dequantised values are exact in bf16.
+void launch_attention_fp4(const AttnArgs& a, const KvMx4& kq, hipStream_t s);
+void launch_kv_dequant_fp4(const void* k_codes, const void* v_codes, const KvMx4& kq, const int* past_dev, int B,
+                           int slot, int n_head, int head_dim, int max_ctx, int lmax, int past_max, hipStream_t s);
+void launch_kv_quant_fp4(void* k_codes, void* v_codes, const KvMx4& kq, const int* past_dev, int B, int S, int slot,
+                         int n_head, int head_dim, int max_ctx, int lmax, hipStream_t s);
+
 // ---- KV row fork (bs_fork_kv; kv_fork.hip) ----
 // Copy the first npos positions of cache row src_slot to rows [dst_slot, dst_slot + count) in one launch: `base` holds
 // n_lw = layers * 2 images [max_batch][n_head][max_ctx] of pos_bytes each (the codes or values of the whole stage, or
-// the fp32 scales of an int8 cache with pos_bytes = 4); every source chunk of chunk_bytes (16, or 4 for the scales;
+// the fp32 scales of an int8 cache with pos_bytes = 4, or the E8M0 bytes of an MXFP4 cache with pos_bytes =
+// head_dim / 32); every source chunk of chunk_bytes (16, or 4 / 1 for the int8 / MXFP4 scales;
 // it divides npos * pos_bytes and the alignment of every segment start) is loaded once and stored count times.  Grid:
 // one block per 1024 chunks, at most 8 per CU (cus), grid-stride beyond.  The row ranges must not overlap.
 bool kv_fork_supported(int npos, size_t pos_bytes);

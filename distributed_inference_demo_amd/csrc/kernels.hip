@@ -17,6 +17,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "attn_merge.h"
+#include "mx4.h"
 
 // Buffer descriptor over a whole allocation for write-through / L2-coherent (aux = 16: sc1)
 // accesses: the split partials other workgroups of the same launch read.
@@ -3573,13 +3574,6 @@ void launch_ln_rows(const float* x, int row_stride, int row_offset, const void* 
 // its rotation (lane >> 2) & 3 is fixed, and the 16-B activation reads of one dword index fall on 64 different
 // banks within each ds_read_b128 lane group (linear bf16 rows in LDS, 64 B per lane, are 4-way otherwise).
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t mx4_code(float w, float inv) {
-  const float r = fabsf(w) * inv;  // exact: inv is a power of two
-  const uint32_t idx = (uint32_t)(r > 0.25f) + (uint32_t)(r >= 0.75f) + (uint32_t)(r > 1.25f) + (uint32_t)(r >= 1.75f) +
-                       (uint32_t)(r > 2.5f) + (uint32_t)(r >= 3.5f) + (uint32_t)(r > 5.0f);
-  return idx | ((__float_as_uint(w) >> 28) & 8u);
-}
-
 // One thread per block of 32 weights.
 __global__ __launch_bounds__(256) void quantize_mx4_kernel(const bf16* __restrict__ W, uint8_t* __restrict__ Q,
                                                            uint8_t* __restrict__ SC, size_t nblocks, int nb) {
@@ -3592,9 +3586,8 @@ __global__ __launch_bounds__(256) void quantize_mx4_kernel(const bf16* __restric
   float amax = 0.f;
 #pragma unroll
   for (int j = 0; j < 32; j++) amax = fmaxf(amax, fabsf(w[j]));
-  const bool zero = !(amax >= 0x1p-100f);
-  const uint32_t E = zero ? 127u : (__float_as_uint(amax) >> 23) - 2u;
-  const float inv = zero ? 0.f : __uint_as_float((254u - E) << 23);  // 2^(127 - E)
+  float inv;  // 2^(127 - E)
+  const uint32_t E = mx4_block_exp(amax, inv);
   const int rot = (b >> 2) & 3;
   u32x4v rec = {0u, 0u, 0u, 0u};
 #pragma unroll

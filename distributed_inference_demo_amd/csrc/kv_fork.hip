@@ -4,7 +4,8 @@
 // The cache is [layer][K|V][slot][head][pos][hd] (one allocation), so a row's cached prefix is L * 2 * n_head
 // segments of npos * hd * esz contiguous bytes, one every max_ctx * hd * esz bytes inside the row and one row every
 // n_head of those.  The kernel walks the flattened list of fixed-size chunks of all segments (16 bytes for codes and
-// values, 4 bytes for the int8 cache's fp32 scales, whose segments start on no wider boundary): a grid-stride loop
+// values, 4 bytes for the int8 cache's fp32 scales and 1 byte for the MXFP4 cache's E8M0 bytes, whose segments start
+// on no wider boundary; the latter are 2 to 4 bytes per position, a byte load and store per lane): a grid-stride loop
 // over tiles of 256 * kForkU chunks.  Every lane issues its kForkU loads before its first store and stores each
 // loaded chunk `count` times, so the source is read once whatever the fan-out.  Plain vector loads and stores (with
 // non-temporal hints the fork measured slower at 11 of 12 points, up to 1.4x at count 7: profiles/kv_fork_ab.txt);
@@ -91,5 +92,6 @@ void launch_kv_fork(void* base, int chunk_bytes, int n_lw, int n_head, int max_b
   if (!g.total) return;
   if (cus <= 0) cus = 256;
   if (chunk_bytes == 16) fork_launch<fork_u4>((char*)base, g, cus, s);
-  else fork_launch<unsigned int>((char*)base, g, cus, s);
+  else if (chunk_bytes == 4) fork_launch<unsigned int>((char*)base, g, cus, s);
+  else fork_launch<unsigned char>((char*)base, g, cus, s);  // the MXFP4 cache's E8M0 bytes: 2 to 4 per position
 }

@@ -187,7 +187,14 @@ struct bs_stage {
   int bf16 = 1;
   int q8 = 0;              // BS_FLAG_INT8_WEIGHTS: block matrices int8 + row scales
   int mx4 = 0;             // BS_FLAG_MXFP4_WEIGHTS: block matrices E2M1 codes + E8M0 block scales
-  int kv8 = 0;             // BS_FLAG_INT8_KV: int8 KV codes + fp32 scales, bf16 staging (kv_int8.hip)
+  // the KV cache's format: the stage's dtype, BS_FLAG_INT8_KV (int8 codes + one fp32 scale per vector, kv_int8.hip) or
+  // BS_FLAG_MXFP4_KV (E2M1 codes + one E8M0 byte per 32 dims, kv_mxfp4.hip); the quantised ones keep a bf16 staging
+  enum KvFormat { KV_PLAIN = 0, KV_INT8, KV_MXFP4 };
+  KvFormat kvf = KV_PLAIN;
+  size_t kv_pos_bytes() const {  // codes or values of one (position, head) vector
+    return kvf == KV_INT8 ? (size_t)hd : kvf == KV_MXFP4 ? (size_t)hd / 2 : (size_t)hd * esz;
+  }
+  size_t kv_pos_scale_bytes() const { return kvf == KV_INT8 ? 4 : kvf == KV_MXFP4 ? (size_t)hd / 32 : 0; }
   size_t esz = 2;
   void* wtmp = nullptr;    // int8 / MXFP4 stages: bf16 [4h][h] staging (init) and dequantized operand (prefill)
   int hd = 0, L = 0;
@@ -205,11 +212,11 @@ struct bs_stage {
   int n_labels = 0;
   std::vector<Layer> layers;
   char* kv = nullptr;  // [L][2][max_batch][heads][max_ctx][hd]
-  // BS_FLAG_INT8_KV: kv holds the int8 codes in that layout (kv_half / kv_layer_stride in bytes of codes), then the
-  // fp32 scales [L][2][max_batch][heads][max_ctx] at kv_scales; kv_stage: two bf16 staging buffers (K, V) of
-  // kv_stage_cap positions x hidden each, shared by the layers
-  float* kv_scales = nullptr;
-  size_t kv_sc_half = 0;       // scales of K (or V) of one layer
+  // Quantised formats: kv holds the codes in that layout (kv_half / kv_layer_stride in bytes of codes), then the
+  // scales [L][2][max_batch][heads][max_ctx] of kv_pos_scale_bytes() each at kv_scales; kv_stage: two bf16 staging
+  // buffers (K, V) of kv_stage_cap positions x hidden each, shared by the layers
+  char* kv_scales = nullptr;
+  size_t kv_sc_half = 0;       // scale bytes of K (or V) of one layer
   char* kv_stage = nullptr;
   size_t kv_stage_cap = 0;
   size_t kvbytes = 0;
@@ -409,12 +416,16 @@ static int validate(const bs_stage_desc* d, bool from_file = false) {
     return fail(BS_ERR_INVALID, "head vocab slice must be a 16-aligned sub-range of [0, vocab)");
   if (!from_file && d->weight_source != BS_WEIGHTS_SYNTHETIC && d->weight_source != BS_WEIGHTS_HOST)
     return fail(BS_ERR_INVALID, "unknown weight_source");
-  if (d->flags & ~(BS_FLAG_INT8_WEIGHTS | BS_FLAG_CLASSIFIER | BS_FLAG_INT8_KV | BS_FLAG_MXFP4_WEIGHTS))
+  if (d->flags & ~(BS_FLAG_INT8_WEIGHTS | BS_FLAG_CLASSIFIER | BS_FLAG_INT8_KV | BS_FLAG_MXFP4_WEIGHTS | BS_FLAG_MXFP4_KV))
     return fail(BS_ERR_INVALID, "unknown desc flags");
   if ((d->flags & BS_FLAG_INT8_KV) && d->dtype != BS_DT_BFLOAT16)
     return fail(BS_ERR_INVALID, "BS_FLAG_INT8_KV needs dtype BFLOAT16");
   if ((d->flags & BS_FLAG_INT8_KV) && hd % 16)
     return fail(BS_ERR_UNSUPPORTED, "BS_FLAG_INT8_KV needs head_dim to be a multiple of 16");
+  if ((d->flags & BS_FLAG_MXFP4_KV) && (d->dtype != BS_DT_BFLOAT16 || (d->flags & BS_FLAG_INT8_KV)))
+    return fail(BS_ERR_INVALID, "BS_FLAG_MXFP4_KV needs dtype BFLOAT16 and excludes BS_FLAG_INT8_KV");
+  if ((d->flags & BS_FLAG_MXFP4_KV) && hd % 32)
+    return fail(BS_ERR_UNSUPPORTED, "BS_FLAG_MXFP4_KV needs head_dim to be a multiple of 32");
   if (d->flags & BS_FLAG_CLASSIFIER) {
     if (!d->is_last) return fail(BS_ERR_INVALID, "BS_FLAG_CLASSIFIER needs the last stage");
     if (d->n_labels < 1 || d->n_labels > 64) return fail(BS_ERR_INVALID, "n_labels must be in [1, 64]");
@@ -561,7 +572,7 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   s->bf16 = desc->dtype == BS_DT_BFLOAT16;
   s->q8 = (desc->flags & BS_FLAG_INT8_WEIGHTS) != 0;
   s->mx4 = (desc->flags & BS_FLAG_MXFP4_WEIGHTS) != 0;
-  s->kv8 = (desc->flags & BS_FLAG_INT8_KV) != 0;
+  s->kvf = (desc->flags & BS_FLAG_INT8_KV) ? bs_stage::KV_INT8 : (desc->flags & BS_FLAG_MXFP4_KV) ? bs_stage::KV_MXFP4 : bs_stage::KV_PLAIN;
   s->esz = s->bf16 ? 2 : 4;
   s->n_labels = (desc->flags & BS_FLAG_CLASSIFIER) ? desc->n_labels : 0;
   s->hd = desc->hidden / desc->n_head;
@@ -726,20 +737,19 @@ static int init_stage(const bs_stage_desc* desc, bs_stage** out, const st::Check
   }
 
   // ---- KV cache
-  s->kv_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx * s->hd * (s->kv8 ? 1 : s->esz);
+  s->kv_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx * s->kv_pos_bytes();
   s->kv_layer_stride = 2 * s->kv_half;
   s->kvbytes = s->kv_layer_stride * (s->L > 0 ? s->L : 0);
-  if (s->kv8) {  // the scales follow the codes (16-B aligned: head_dim % 16 == 0)
-    s->kv_sc_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx;
-    s->kvbytes += 2 * s->kv_sc_half * 4 * (s->L > 0 ? s->L : 0);
-  }
+  // the scales follow the codes (16-B aligned: a position's codes are a multiple of 16 bytes)
+  s->kv_sc_half = (size_t)desc->max_batch * desc->n_head * desc->max_ctx * s->kv_pos_scale_bytes();
+  s->kvbytes += 2 * s->kv_sc_half * (s->L > 0 ? s->L : 0);
   if (s->kvbytes) {
     if (!owned_alloc(s, s->kvbytes, false, (void**)&s->kv))
       return cleanup(fail(BS_ERR_OOM, "KV cache allocation failed (" + std::to_string(s->kvbytes) + " B)"));
     if (hipMemsetAsync(s->kv, 0, s->kvbytes, s->own) != hipSuccess) return cleanup(fail(BS_ERR_DEVICE, "kv memset"));
-    if (s->kv8) s->kv_scales = (float*)(s->kv + s->kv_layer_stride * s->L);
+    if (s->kvf) s->kv_scales = s->kv + s->kv_layer_stride * s->L;
   }
-  if (s->kv8 && s->L > 0) {  // bf16 staging of a call's new K / V rows (and, for S > 1, the dequantised past)
+  if (s->kvf && s->L > 0) {  // bf16 staging of a call's new K / V rows (and, for S > 1, the dequantised past)
     s->kv_stage_cap = std::max<size_t>(T, desc->max_ctx);
     const size_t sb = 2 * s->kv_stage_cap * h * 2;
     if (!owned_alloc(s, sb, true, (void**)&s->kv_stage))
@@ -873,20 +883,31 @@ extern "C" int bs_read_kv(const bs_stage* s, int32_t layer, int32_t slot, int32_
   HIP_TRY(hipStreamSynchronize(s->own));
   const int nh = s->d.n_head, hd = s->hd;
   const size_t run = (size_t)npos * hd;  // contiguous elements of one (K|V, head)
-  std::vector<uint16_t> tmp(s->bf16 && !s->kv8 ? run : 0);
-  std::vector<int8_t> qtmp(s->kv8 ? run : 0);
-  std::vector<float> stmp(s->kv8 ? npos : 0);
+  std::vector<uint16_t> tmp(s->bf16 && !s->kvf ? run : 0);
+  const size_t pb = s->kv_pos_bytes(), psb = s->kv_pos_scale_bytes();
+  std::vector<uint8_t> qtmp(s->kvf ? (size_t)npos * pb : 0), stmp((size_t)npos * psb);
   for (int w = 0; w < 2; w++)
     for (int hh = 0; hh < nh; hh++) {
       const size_t e0 = (((size_t)slot * nh + hh) * s->d.max_ctx + pos0) * hd;
-      if (s->kv8) {  // dequantised values: (float)q * scale
+      if (s->kvf) {  // dequantised values: (float)q * scale, or +-grid * 2^(E - 127)
         float* dq = out + ((size_t)w * nh + hh) * run;
         if (!run) continue;
-        HIP_TRY(hipMemcpy(qtmp.data(), s->kv + layer * s->kv_layer_stride + w * s->kv_half + e0, run,
+        HIP_TRY(hipMemcpy(qtmp.data(), s->kv + layer * s->kv_layer_stride + w * s->kv_half + e0 / hd * pb, qtmp.size(),
                           hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(stmp.data(), s->kv_scales + ((size_t)layer * 2 + w) * s->kv_sc_half + e0 / hd,
-                          (size_t)npos * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < run; i++) dq[i] = (float)qtmp[i] * stmp[i / hd];
+        HIP_TRY(hipMemcpy(stmp.data(), s->kv_scales + ((size_t)layer * 2 + w) * s->kv_sc_half + e0 / hd * psb,
+                          stmp.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < run; i++) {
+          if (s->kvf == bs_stage::KV_INT8) {
+            float sc;
+            std::memcpy(&sc, &stmp[i / hd * 4], 4);
+            dq[i] = (float)(int8_t)qtmp[i] * sc;
+          } else {
+            static const float grid[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
+            const unsigned c = (qtmp[i / 2] >> (4 * (i & 1))) & 15u;
+            const float mag = std::ldexp(grid[c & 7], (int)stmp[i / 32] - 127);
+            dq[i] = (c & 8) ? -mag : mag;
+          }
+        }
         continue;
       }
       const char* src = s->kv + layer * s->kv_layer_stride + w * s->kv_half + e0 * s->esz;
@@ -910,17 +931,17 @@ extern "C" int bs_reset_kv(bs_stage* s, int32_t slot) {
   HIP_TRY(hipSetDevice(s->d.device));
   // Cached positions are addressed by past_len, so forgetting is bookkeeping only; zero the
   // rows anyway so stale data can never be read by a caller that reuses past_len wrongly.
-  const size_t row = (size_t)s->d.n_head * s->d.max_ctx * s->hd * (s->kv8 ? 1 : s->esz);
-  const size_t srow = (size_t)s->d.n_head * s->d.max_ctx;  // int8 KV: scales of one row
+  const size_t row = (size_t)s->d.n_head * s->d.max_ctx * s->kv_pos_bytes();
+  const size_t srow = (size_t)s->d.n_head * s->d.max_ctx * s->kv_pos_scale_bytes();  // quantised: scale bytes of one row
   for (int l = 0; l < s->L; l++)
     for (int w = 0; w < 2; w++) {
       char* base = s->kv + l * s->kv_layer_stride + w * s->kv_half;
       if (slot < 0) HIP_TRY(hipMemsetAsync(base, 0, s->kv_half, s->own));
       else HIP_TRY(hipMemsetAsync(base + (size_t)slot * row, 0, row, s->own));
-      if (!s->kv8) continue;
-      float* sc = s->kv_scales + ((size_t)l * 2 + w) * s->kv_sc_half;
-      if (slot < 0) HIP_TRY(hipMemsetAsync(sc, 0, s->kv_sc_half * 4, s->own));
-      else HIP_TRY(hipMemsetAsync(sc + (size_t)slot * srow, 0, srow * 4, s->own));
+      if (!s->kvf) continue;
+      char* sc = s->kv_scales + ((size_t)l * 2 + w) * s->kv_sc_half;
+      if (slot < 0) HIP_TRY(hipMemsetAsync(sc, 0, s->kv_sc_half, s->own));
+      else HIP_TRY(hipMemsetAsync(sc + (size_t)slot * srow, 0, srow, s->own));
     }
   if (s->px_active) {  // the row's prefix declaration goes with its content
     const int r0 = slot < 0 ? 0 : slot, n = slot < 0 ? s->d.max_batch : 1;
@@ -948,7 +969,7 @@ extern "C" int bs_reset_kv(bs_stage* s, int32_t slot) {
 extern "C" int bs_set_row_prefix(bs_stage* s, int32_t slot, int32_t count, int32_t src_slot, int32_t npos, void* stream) {
   if (!s) return fail(BS_ERR_INVALID, "stage is NULL");
   if (!s->bf16) return fail(BS_ERR_UNSUPPORTED, "bs_set_row_prefix needs a bf16 stage");
-  if (s->kv8) return fail(BS_ERR_UNSUPPORTED, "bs_set_row_prefix on an int8 KV cache is not supported");
+  if (s->kvf) return fail(BS_ERR_UNSUPPORTED, "bs_set_row_prefix on a quantised KV cache is not supported");
   if (s->hd > 128) return fail(BS_ERR_UNSUPPORTED, "bs_set_row_prefix needs head_dim <= 128");
   const int mb = s->d.max_batch;
   if (count <= 0 || slot < 0 || slot > mb - count) return fail(BS_ERR_INVALID, "slot range outside max_batch");
@@ -994,7 +1015,7 @@ extern "C" int bs_fork_kv(bs_stage* s, int32_t src_slot, int32_t dst_slot, int32
   if (npos > s->d.max_ctx) return fail(BS_ERR_INVALID, "npos beyond max_ctx");
   if (src_slot >= dst_slot && src_slot - dst_slot < count) return fail(BS_ERR_INVALID, "the source row is one of the destination rows");
   if (!count || !npos || s->L <= 0) return BS_OK;
-  const size_t pos_bytes = (size_t)s->hd * (s->kv8 ? 1 : s->esz);  // a multiple of 16 (head_dim % 8, % 16 for int8)
+  const size_t pos_bytes = s->kv_pos_bytes();  // a multiple of 16 (head_dim % 8, % 16 for int8, % 32 for MXFP4)
   if (!kv_fork_supported(npos, pos_bytes)) return fail(BS_ERR_UNSUPPORTED, "npos * head_dim too large for the fork kernel");
   HIP_TRY(hipSetDevice(s->d.device));
   if (s->cus <= 0 && hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, s->d.device) != hipSuccess) {
@@ -1003,8 +1024,9 @@ extern "C" int bs_fork_kv(bs_stage* s, int32_t src_slot, int32_t dst_slot, int32
   }
   hipStream_t st = stream ? (hipStream_t)stream : s->own;
   launch_kv_fork(s->kv, 16, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, pos_bytes, src_slot, dst_slot, count, npos, s->cus, st);
-  if (s->kv8)  // scale segments start on 4-byte boundaries only
-    launch_kv_fork(s->kv_scales, 4, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, 4, src_slot, dst_slot, count, npos, s->cus, st);
+  if (s->kvf)  // scale segments start on 4-byte (int8) or 1-byte (MXFP4) boundaries only
+    launch_kv_fork(s->kv_scales, s->kvf == bs_stage::KV_INT8 ? 4 : 1, 2 * s->L, s->d.n_head, mb, s->d.max_ctx,
+                   s->kv_pos_scale_bytes(), src_slot, dst_slot, count, npos, s->cus, st);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(BS_ERR_DEVICE, std::string("kv fork: ") + hipGetErrorString(err));
   return BS_OK;
@@ -1031,7 +1053,7 @@ extern "C" int bs_copy_kv(bs_stage* s, const int32_t* src_slots, const int32_t* 
     }
   }
   if (!count || !npos || s->L <= 0) return BS_OK;
-  const size_t pos_bytes = (size_t)s->hd * (s->kv8 ? 1 : s->esz);  // a multiple of 16 (head_dim % 8, % 16 for int8)
+  const size_t pos_bytes = s->kv_pos_bytes();  // a multiple of 16 (head_dim % 8, % 16 for int8, % 32 for MXFP4)
   if (!kv_fork_supported(npos, pos_bytes)) return fail(BS_ERR_UNSUPPORTED, "npos * head_dim too large for the copy kernel");
   HIP_TRY(hipSetDevice(s->d.device));
   if (s->cus <= 0 && hipDeviceGetAttribute(&s->cus, hipDeviceAttributeMultiprocessorCount, s->d.device) != hipSuccess) {
@@ -1043,8 +1065,9 @@ extern "C" int bs_copy_kv(bs_stage* s, const int32_t* src_slots, const int32_t* 
     int n = 1;  // pairs i .. i + n - 1: one source, destinations dst, dst + 1, ...
     while (i + n < count && src_slots[i + n] == src_slots[i] && dst_slots[i + n] == dst_slots[i] + n) n++;
     launch_kv_fork(s->kv, 16, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, pos_bytes, src_slots[i], dst_slots[i], n, npos, s->cus, st);
-    if (s->kv8)  // scale segments start on 4-byte boundaries only
-      launch_kv_fork(s->kv_scales, 4, 2 * s->L, s->d.n_head, mb, s->d.max_ctx, 4, src_slots[i], dst_slots[i], n, npos, s->cus, st);
+    if (s->kvf)  // scale segments start on 4-byte (int8) or 1-byte (MXFP4) boundaries only
+      launch_kv_fork(s->kv_scales, s->kvf == bs_stage::KV_INT8 ? 4 : 1, 2 * s->L, s->d.n_head, mb, s->d.max_ctx,
+                     s->kv_pos_scale_bytes(), src_slots[i], dst_slots[i], n, npos, s->cus, st);
     i += n;
   }
   hipError_t err = hipGetLastError();
@@ -1474,11 +1497,14 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
     // position per (row, head) at static arguments (graph-capturable), S > 1 lays each row out as the prefill
     // attention reads it: its dequantised past, then the new positions at past_b ..
     KvQ8 kq{};
+    KvMx4 kx{};
     const int past_max = *std::max_element(pasts.begin(), pasts.end());
     const int lmax = S == 1 ? 1 : past_max + S;
-    if (s->kv8) {
-      kq.k_scale = s->kv_scales + (size_t)l * 2 * s->kv_sc_half; kq.v_scale = kq.k_scale + s->kv_sc_half;
+    if (s->kvf) {
+      char* sc = s->kv_scales + (size_t)l * 2 * s->kv_sc_half;
+      kq.k_scale = (float*)sc; kq.v_scale = (float*)(sc + s->kv_sc_half);
       kq.k_stage = (bf16*)s->kv_stage; kq.v_stage = kq.k_stage + s->kv_stage_cap * h;
+      kx = KvMx4{(uint8_t*)sc, (uint8_t*)sc + s->kv_sc_half, kq.k_stage, kq.v_stage};
       e.k_cache = kq.k_stage; e.v_cache = kq.v_stage; e.slot = 0; e.max_ctx = lmax;
       if (S == 1) { e.past_dev = nullptr; e.past = 0; }
     }
@@ -1528,19 +1554,23 @@ static int enqueue_forward(bs_stage* s, const bs_step* step, const Tail& tail, c
       av.part_acc = s->vf_acc; av.part_ml = s->vf_ml; av.max_chunks = s->vf_stride;
       if (tree) launch_attention_tree(av, s->tr_table, st);  // the same grid and partials on the matrix cores (attn_tree.hip)
       else launch_attention_verify(s->bf16, av, st);
-    } else if (!s->kv8) {
+    } else if (!s->kvf) {
       ProfScope p(s, st, 3, ctx_sum * nh * hd * 2 * s->esz);
       launch_attention(s->bf16, a, st);
     } else if (S == 1) {
-      ProfScope p(s, st, 3, ctx_sum * nh * 2 * (hd + 4));
-      launch_attention_q8(a, kq, st);
+      ProfScope p(s, st, 3, ctx_sum * nh * 2 * (double)(s->kv_pos_bytes() + s->kv_pos_scale_bytes()));
+      if (s->kvf == bs_stage::KV_INT8) launch_attention_q8(a, kq, st);
+      else launch_attention_fp4(a, kx, st);
     } else {
-      ProfScope p(s, st, 3, ctx_sum * nh * 2 * (hd + 4));
-      launch_kv_dequant(kbase, kbase + s->kv_half, kq, past_dev, B, slot, nh, hd, d.max_ctx, lmax, past_max, st);
+      ProfScope p(s, st, 3, ctx_sum * nh * 2 * (double)(s->kv_pos_bytes() + s->kv_pos_scale_bytes()));
+      const bool i8 = s->kvf == bs_stage::KV_INT8;
+      if (i8) launch_kv_dequant(kbase, kbase + s->kv_half, kq, past_dev, B, slot, nh, hd, d.max_ctx, lmax, past_max, st);
+      else launch_kv_dequant_fp4(kbase, kbase + s->kv_half, kx, past_dev, B, slot, nh, hd, d.max_ctx, lmax, past_max, st);
       AttnArgs as = a;
       as.k_cache = kq.k_stage; as.v_cache = kq.v_stage; as.slot = 0; as.max_ctx = lmax;
       launch_attention(1, as, st);
-      launch_kv_quant(kbase, kbase + s->kv_half, kq, past_dev, B, S, slot, nh, hd, d.max_ctx, lmax, st);
+      if (i8) launch_kv_quant(kbase, kbase + s->kv_half, kq, past_dev, B, S, slot, nh, hd, d.max_ctx, lmax, st);
+      else launch_kv_quant_fp4(kbase, kbase + s->kv_half, kx, past_dev, B, S, slot, nh, hd, d.max_ctx, lmax, st);
     }
     if (a.defer_merge) {
       const AttnParts parts{s->part_acc, s->part_ml, nsplit, nh, hd, s->max_chunks, slot};
@@ -2292,10 +2322,10 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
   for (int b = 0; s->px_active && b < B; b++)
     if (pasts[b] < s->px_host[slot + b].npos)
       return fail(BS_ERR_INVALID, "past_len below the row's shared prefix (bs_set_row_prefix)");
-  if (s->kv8 && S > 1 && s->L > 0) {  // every row's past and new positions side by side in the bf16 staging
+  if (s->kvf && S > 1 && s->L > 0) {  // every row's past and new positions side by side in the bf16 staging
     const size_t need = (size_t)B * (*std::max_element(pasts.begin(), pasts.end()) + S);
     if (need > s->kv_stage_cap)
-      return fail(BS_ERR_UNSUPPORTED, "int8 KV: batch * (longest past_len + seq) = " + std::to_string(need) +
+      return fail(BS_ERR_UNSUPPORTED, "quantised KV: batch * (longest past_len + seq) = " + std::to_string(need) +
                                           " positions exceed the staging capacity of " +
                                           std::to_string(s->kv_stage_cap) + " (max(max_tokens, max_ctx))");
   }
@@ -2310,7 +2340,7 @@ static int forward_impl(bs_stage* s, const bs_step* step, const void* in, void* 
                                        : "a verify pass needs 2 <= seq <= 8 and batch * seq <= 32");
     if (tree && !s->bf16) return fail(BS_ERR_UNSUPPORTED, "bs_forward_tree needs a BFLOAT16 stage");
     if (tree && s->hd % 8) return fail(BS_ERR_UNSUPPORTED, "bs_forward_tree needs head_dim % 8 == 0");
-    if (s->kv8) return fail(BS_ERR_UNSUPPORTED, "BS_STEP_VERIFY on an int8 KV cache is not supported");
+    if (s->kvf) return fail(BS_ERR_UNSUPPORTED, "BS_STEP_VERIFY on a quantised KV cache is not supported");
     if (s->hd > 128) return fail(BS_ERR_UNSUPPORTED, "BS_STEP_VERIFY needs head_dim <= 128");
     if (s->n_labels) return fail(BS_ERR_STATE, "BS_STEP_VERIFY on a classifier stage");
     if (s->top_k > 1) return fail(BS_ERR_STATE, "BS_STEP_VERIFY needs the greedy pick (bs_set_sampling top_k <= 1)");
@@ -2503,7 +2533,7 @@ extern "C" int bs_compact_kv(bs_stage* s, int32_t slot, int32_t past, const int3
     identity = identity && src[k] == k;
   }
   if (n && (long)past + src[n - 1] >= s->d.max_ctx) return fail(BS_ERR_INVALID, "past + src beyond max_ctx");
-  if (!s->bf16 || s->kv8) return fail(BS_ERR_UNSUPPORTED, "bs_compact_kv needs a BFLOAT16 stage with a bf16 KV cache");
+  if (!s->bf16 || s->kvf) return fail(BS_ERR_UNSUPPORTED, "bs_compact_kv needs a BFLOAT16 stage with a bf16 KV cache");
   if (s->hd > 128 || s->hd % 8) return fail(BS_ERR_UNSUPPORTED, "bs_compact_kv needs head_dim % 8 == 0 and <= 128");
   if (identity || s->L <= 0) return BS_OK;
   HIP_TRY(hipSetDevice(s->d.device));
@@ -2613,7 +2643,7 @@ extern "C" int bs_forward_ragged(bs_stage* s, const bs_ragged_step* step, const 
     return fail(BS_ERR_INVALID, "rows must be positive and slots / seq_lens / past_lens non-NULL");
   if (!in || !out) return fail(BS_ERR_INVALID, "in/out is NULL");
   if (!s->bf16) return fail(BS_ERR_UNSUPPORTED, "bs_forward_ragged needs a BFLOAT16 stage");
-  if (s->kv8) return fail(BS_ERR_UNSUPPORTED, "bs_forward_ragged on an int8 KV cache is not supported");
+  if (s->kvf) return fail(BS_ERR_UNSUPPORTED, "bs_forward_ragged on a quantised KV cache is not supported");
   if (s->hd > 128 || s->hd % 8) return fail(BS_ERR_UNSUPPORTED, "bs_forward_ragged needs head_dim % 8 == 0 and <= 128");
   if (s->n_labels) return fail(BS_ERR_STATE, "bs_forward_ragged on a classifier stage");
   if (s->top_k > 1) return fail(BS_ERR_STATE, "bs_forward_ragged needs the greedy pick (bs_set_sampling top_k <= 1)");

@@ -647,11 +647,12 @@ def connect_p2p(rank, world, head_split, groups, device):
 
 def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb_rows=1, n_mb=None, max_ctx=1024,
                max_seq=512, seed=0, head_split=None, executor_factory=None, n_labels=0, kv_int8=False, sample=False,
-               extra_rows=0):
+               extra_rows=0, kv_mxfp4=False):
     """Create this rank's stage (server.py:893-905 layer range, plus a vocabulary slice of the
     tied lm_head when head_split) and its Pipeline.  n_labels > 0: the last stage is a sequence-classification
     tail (BS_FLAG_CLASSIFIER; `classify` runs the task) and there is no head ring.  kv_int8: every stage keeps an
-    int8 KV cache (BS_FLAG_INT8_KV; bf16 stages of the HIP library only).  sample: the run samples per row
+    int8 KV cache (BS_FLAG_INT8_KV; bf16 stages of the HIP library only); kv_mxfp4: an MXFP4 one (BS_FLAG_MXFP4_KV),
+    under the same three conditions.  sample: the run samples per row
     (Pipeline.set_row_sampler), which needs the whole lm_head on the last stage, as `score` does: no head ring.
     extra_rows: KV rows of the stage beyond the pool's mb_rows * n_mb (max_batch = mb_rows * n_mb + extra_rows); the
     first of them is Pipeline.template_slot, the shared-prefix template that fork_row copies from.
@@ -675,13 +676,16 @@ def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb
         raise ValueError(f"{model.name}: weight-only int8 stages need dtype bf16 (got {dtype})")
     if model.mxfp4_weights and dtype != "bf16":
         raise ValueError(f"{model.name}: weight-only MXFP4 stages need dtype bf16 (got {dtype})")
-    if kv_int8 and dtype != "bf16":
-        raise ValueError(f"an int8 KV cache needs dtype bf16 (got {dtype})")
-    if kv_int8 and executor_factory is not None:
-        raise ValueError("an int8 KV cache is the HIP stage's: not available with an executor_factory")
+    if kv_int8 and kv_mxfp4:
+        raise ValueError("kv_int8 and kv_mxfp4 are two formats of one cache: pass one")
+    kvq = "an int8" if kv_int8 else "an MXFP4" if kv_mxfp4 else None
+    if kvq and dtype != "bf16":
+        raise ValueError(f"{kvq} KV cache needs dtype bf16 (got {dtype})")
+    if kvq and executor_factory is not None:
+        raise ValueError(f"{kvq} KV cache is the HIP stage's: not available with an executor_factory")
     lb, le = stage_ranges(world, model.n_layer)[rank]
-    if kv_int8 and le <= lb:  # defensive: stage_ranges gives every rank a layer (checked above)
-        raise ValueError("an int8 KV cache on a stage that holds only a vocabulary slice (no layers, no cache)")
+    if kvq and le <= lb:  # defensive: stage_ranges gives every rank a layer (checked above)
+        raise ValueError(f"{kvq} KV cache on a stage that holds only a vocabulary slice (no layers, no cache)")
     is_first, is_last = rank == 0, rank == world - 1
     hslice = vocab_slices(model.vocab, world)[rank] if head_split else None
     if executor_factory is None:
@@ -690,7 +694,7 @@ def build_rank(model: config.BloomDims, rank, world, device, *, dtype="bf16", mb
                    device=device.index if device.type == "cuda" else 0, max_batch=mb_rows * n_mb + extra_rows,
                    max_ctx=max_ctx, max_tokens=mb_rows * max_seq, seed=seed, is_first=is_first,
                    is_last=is_last and not head_split, head_slice=hslice, int8_weights=model.int8_weights,
-                   n_labels=n_labels if is_last else 0, kv_int8=kv_int8, mxfp4_weights=model.mxfp4_weights)
+                   n_labels=n_labels if is_last else 0, kv_int8=kv_int8, mxfp4_weights=model.mxfp4_weights, kv_mxfp4=kv_mxfp4)
         ex = StageExecutor(st)
     else:
         kw = {"n_labels": n_labels} if (n_labels and is_last) else {}

@@ -59,7 +59,7 @@ its first P positions as the template row's (bs_set_row_prefix) until it is rele
 declare the prompt as the sample's first row's; a decode step whose 2 .. 32 rows all hold the same declaration then
 streams the shared positions once per head on the matrix cores instead of once per row.  Same tokens as without the
 option up to bf16 rounding of the context; a micro-batch whose rows do not all hold the declaration (a row idle or not
-yet admitted) runs the plain route.  Not with --kv int8.  It adds one launch per layer; on MI355X the decode step was
+yet admitted) runs the plain route.  Not with --kv int8 / mxfp4.  It adds one launch per layer; on MI355X the decode step was
 faster at every measured shape (bloom-7b1 / 1b1, 4 .. 32 rows, prefixes 256 .. 1984: 0.50x .. 0.995x the plain step's
 time), the gain growing with rows x prefix; beam search of 4 hypotheses end to end did not change.
 --num-beams W is beam search on one GPU (beam.py; no counterpart in the reference): the samples are decoded one after
@@ -87,7 +87,7 @@ samples, since samples admitted together also finish together -- are prefilled b
 each row at its own length, the stage's weights streamed once for the wave instead of once per sample), and each
 sample's first token comes from it.  Plain greedy generation on one rank with the HIP stage, bf16, kv bf16: not with
 --sample, the logit processor or guide options, --shared-prefix, --speculate, --sample-speculate, --num-beams, --score,
---kv int8 or --prefill 0.  Same tokens as without the option up to bf16 rounding of the attention context.
+--kv int8 / mxfp4 or --prefill 0.  Same tokens as without the option up to bf16 rounding of the attention context.
 --adapters N --adapter-rank R [--adapter-seed S] [--adapter-amplitude A] (opt-in) is per-row LoRA serving on one GPU with the
 HIP stage: N synthetic adapters of rank R on query_key_value, dense and dense_4h_to_h are loaded once (bs_load_adapter);
 sample i names adapter i % (N + 1) - 1 (every (N + 1)-th sample runs the base model), set at admission beside the
@@ -133,7 +133,8 @@ class RunConfig:
     seed: int = 0                 # weight generator seed
     head_split: bool = True       # vocabulary-parallel lm_head ring when world > 1
     prefill: bool = True          # an admitted sample's prompt as one prefill pass of its row (else a token a round)
-    kv: str = "bf16"              # KV cache storage: "bf16", or "int8" (BS_FLAG_INT8_KV: about half the cache bytes)
+    kv: str = "bf16"              # KV cache storage: "bf16", "int8" (BS_FLAG_INT8_KV: about half the cache bytes) or
+                                  # "mxfp4" (BS_FLAG_MXFP4_KV: about a quarter; 4-bit, lossy, head_dim % 32 == 0)
     score: bool = False           # the scoring task: each prompt's log-likelihood and perplexity, one pass a sample
     speculate: int = 0            # speculative decoding: tokens drafted per verify pass (0 = off; one GPU only)
     draft: str = "ngram"          # the drafter: "ngram" (prompt lookup) or a draft model's name (same vocabulary)
@@ -215,7 +216,7 @@ class RunConfig:
                 ("sample", self.sample), ("the logit processors", self.processors), ("guide_file / choice", self.guided),
                 ("shared_prefix", self.shared_prefix), ("speculate", self.speculate),
                 ("sample_speculate", self.sample_speculate), ("num_beams", self.num_beams), ("score", self.score),
-                ("max_length == 0", self.max_length <= 0), ("kv = 'int8'", self.kv == "int8"),
+                ("max_length == 0", self.max_length <= 0), ("kv = 'int8' / 'mxfp4'", self.kv != "bf16"),
                 ("prefill = False", not self.prefill), ("dtype != 'bf16'", self.dtype != "bf16")) if on]
             if bad:
                 raise ValueError("ragged_admission is plain greedy generation with admission prefills on a bf16 stage "
@@ -227,7 +228,7 @@ class RunConfig:
                 ("speculate", self.speculate), ("sample", self.sample), ("sample_speculate", self.sample_speculate),
                 ("a draft model (draft != 'ngram')", self.draft != "ngram"), ("the logit processors", self.processors),
                 ("guide_file / choice", self.guided), ("shared_prefix", self.shared_prefix), ("num_beams", self.num_beams),
-                ("score", self.score), ("max_length == 0", self.max_length <= 0), ("kv = 'int8'", self.kv == "int8"),
+                ("score", self.score), ("max_length == 0", self.max_length <= 0), ("kv = 'int8' / 'mxfp4'", self.kv != "bf16"),
                 ("ragged_admission", self.ragged_admission), ("dtype != 'bf16'", self.dtype != "bf16")) if on]
             if bad:
                 raise ValueError("speculate_tree is greedy tree speculative decoding with the n-gram drafter on a bf16 "
@@ -274,8 +275,8 @@ class RunConfig:
             if not ((self.shared_prefix and self.prefix_fork) or self.num_beams):
                 raise ValueError("prefix_attention needs rows that share cached positions: shared_prefix with "
                                  "prefix_fork, or num_beams")
-            if self.kv == "int8":
-                raise ValueError("prefix_attention needs kv = 'bf16' (no shared-prefix attention over an int8 KV cache)")
+            if self.kv != "bf16":
+                raise ValueError("prefix_attention needs kv = 'bf16' (no shared-prefix attention over a quantised KV cache)")
             if self.dtype != "bf16":
                 raise ValueError("prefix_attention needs dtype = 'bf16' (the shared-prefix kernels are bf16)")
         if self.num_beams:
@@ -289,13 +290,13 @@ class RunConfig:
                 raise ValueError(f"eos_id must be a token id or -1 for none (got {self.eos_id})")
             if not float("-inf") < self.length_penalty < float("inf"):
                 raise ValueError(f"length_penalty must be finite (got {self.length_penalty})")
-        if self.kv not in ("bf16", "int8"):
-            raise ValueError(f"kv must be 'bf16' or 'int8' (got {self.kv!r})")
+        if self.kv not in ("bf16", "int8", "mxfp4"):
+            raise ValueError(f"kv must be 'bf16', 'int8' or 'mxfp4' (got {self.kv!r})")
         if self.speculate:
             if not 1 <= self.speculate <= 7:
                 raise ValueError(f"speculate must be in [1, 7] (got {self.speculate}): a verify pass holds 8 positions")
             if self.kv != "bf16":
-                raise ValueError("speculative decoding needs kv = 'bf16' (no verify pass over an int8 KV cache yet)")
+                raise ValueError("speculative decoding needs kv = 'bf16' (no verify pass over a quantised KV cache yet)")
             if self.max_length <= 0:
                 raise ValueError("speculative decoding is a generation task: max_length must be > 0")
             if self.score:
@@ -316,7 +317,7 @@ class RunConfig:
                 raise ValueError(f"sample_speculate must be in [1, 7] (got {self.sample_speculate}): a verify pass "
                                  "holds 8 positions")
             if self.kv != "bf16":
-                raise ValueError("sampled speculative decoding needs kv = 'bf16' (no verify pass over an int8 KV cache yet)")
+                raise ValueError("sampled speculative decoding needs kv = 'bf16' (no verify pass over a quantised KV cache yet)")
 
 
 def request_seed(sample_seed, i):
@@ -473,7 +474,7 @@ def run_rank(cfg: RunConfig, rank, world, device, prompts=None, executor_factory
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + cfg.max_length + 1, max_seq=max_seq, seed=cfg.seed,
                                 head_split=cfg.head_split, executor_factory=executor_factory,
-                                kv_int8=cfg.kv == "int8", sample=cfg.sample or bool(proc) or cfg.guided,
+                                kv_int8=cfg.kv == "int8", kv_mxfp4=cfg.kv == "mxfp4", sample=cfg.sample or bool(proc) or cfg.guided,
                                 extra_rows=int(fork))
     guide_id = pipe.load_guide(guide) if guide is not None else None  # once, outside the decode loop (last rank)
     # per-row LoRA: the adapters are loaded once; sample i names adapter i % (N + 1) - 1 from its admission to its
@@ -623,7 +624,8 @@ def _classify_run(cfg, model, rank, world, device, prompts, lens, executor_facto
     passes = classify_batches(lens, rows)
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + 1, max_seq=max(lens), seed=cfg.seed, head_split=False,
-                                executor_factory=executor_factory, n_labels=cfg.n_labels, kv_int8=cfg.kv == "int8")
+                                executor_factory=executor_factory, n_labels=cfg.n_labels, kv_int8=cfg.kv == "int8",
+                                kv_mxfp4=cfg.kv == "mxfp4")
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "passes": len(passes),
                     "task": "classification", "n_labels": cfg.n_labels})
@@ -672,7 +674,8 @@ def _score_run(cfg, model, rank, world, device, prompts, lens, executor_factory,
     passes = [list(range(k, min(k + rows, cfg.num_sample))) for k in range(0, cfg.num_sample, rows)]
     pipe, (lb, le) = build_rank(model, rank, world, device, dtype=cfg.dtype, mb_rows=mb, n_mb=n_mb,
                                 max_ctx=max(lens) + 1, max_seq=max(lens), seed=cfg.seed, head_split=False,
-                                executor_factory=executor_factory, kv_int8=cfg.kv == "int8")
+                                executor_factory=executor_factory, kv_int8=cfg.kv == "int8",
+                                kv_mxfp4=cfg.kv == "mxfp4")
     say(STATES[0], {"rank_layers": [lb, le], "stages": world, "core_pool_size": cfg.core_pool_size,
                     "micro_batches": n_mb, "rows_per_micro_batch": mb, "passes": len(passes), "task": "score"})
     cuda = device.type == "cuda"
@@ -784,7 +787,8 @@ def _beam_run(cfg, model, device, prompts, lens, say):
         raise ValueError(f"eos_id ({cfg.eos_id}) outside the vocabulary ({model.vocab})")
     stage = Stage(model.hidden, model.n_head, model.n_layer, model.vocab, 0, model.n_layer, dtype=cfg.dtype, device=dev,
                   max_batch=W, max_ctx=max(lens) + cfg.max_length + 1, max_tokens=max(max(lens), W), seed=cfg.seed,
-                  int8_weights=model.int8_weights, mxfp4_weights=model.mxfp4_weights, kv_int8=cfg.kv == "int8")
+                  int8_weights=model.int8_weights, mxfp4_weights=model.mxfp4_weights, kv_int8=cfg.kv == "int8",
+                  kv_mxfp4=cfg.kv == "mxfp4")
     searcher = BeamSearcher([stage], W, length_penalty=cfg.length_penalty, eos=cfg.eos_id,
                             prefix_attention=cfg.prefix_attention)
     say(STATES[0], {"rank_layers": [0, model.n_layer], "stages": 1, "num_beams": W})

@@ -50,6 +50,7 @@ BS_LORA_QKV, BS_LORA_DENSE, BS_LORA_FC2 = 1, 2, 4  # bs_adapter_desc.targets
 BS_FLAG_INT8_WEIGHTS = 1  # bs_stage_desc.flags: weight-only int8 block matrices
 BS_FLAG_CLASSIFIER = 2    # bs_stage_desc.flags: sequence-classification tail (score head, class ids out)
 BS_FLAG_INT8_KV = 4       # bs_stage_desc.flags: int8 KV cache, one fp32 scale per (position, head) vector
+BS_FLAG_MXFP4_KV = 16     # bs_stage_desc.flags: MXFP4 KV cache, one E8M0 byte per 32 dims of a (position, head) vector
 BS_FLAG_MXFP4_WEIGHTS = 8  # bs_stage_desc.flags: weight-only MXFP4 block matrices (E2M1 codes + E8M0 block scales)
 
 DTYPES = {
@@ -269,13 +270,15 @@ class Stage:
     def __init__(self, hidden, n_head, n_layer, vocab, layer_begin, layer_end, *, dtype="bf16", device=0,
                  max_batch=1, max_ctx=2048, max_tokens=0, seed=0, eps=1e-5, host_weights=None,
                  is_first=None, is_last=None, head_slice=None, int8_weights=False, weights_file=None, n_labels=0,
-                 kv_int8=False, mxfp4_weights=False):
+                 kv_int8=False, mxfp4_weights=False, kv_mxfp4=False):
         """weights_file: a safetensors checkpoint (or its sharded *.index.json) of HF BLOOM tensors;
         the stage maps it and loads only its own layer range (bs_init_stage_file).
         n_labels > 0: a sequence-classification tail (BS_FLAG_CLASSIFIER, last stage): forwards return class ids
         and logits [batch][n_labels] instead of tokens and vocabulary logits.
         kv_int8: the KV cache holds int8 codes + one fp32 scale per (position, head) vector (BS_FLAG_INT8_KV, bf16
         stages); read_kv returns the dequantised values.
+        kv_mxfp4: the KV cache holds OCP MXFP4 along head_dim (BS_FLAG_MXFP4_KV, bf16 stages, head_dim % 32 == 0,
+        opt-in: lossy); excludes kv_int8; read_kv returns the dequantised values.
         mxfp4_weights: the four block matrices are held as OCP MXFP4 (BS_FLAG_MXFP4_WEIGHTS, bf16 stages, opt-in:
         round-to-nearest 4-bit weights are lossy); read_weights returns the dequantised values, which are exact in
         bf16, so a plain bf16 stage given them as host_weights is the same model."""
@@ -294,6 +297,8 @@ class Stage:
             d.flags |= BS_FLAG_MXFP4_WEIGHTS
         if kv_int8:
             d.flags |= BS_FLAG_INT8_KV
+        if kv_mxfp4:
+            d.flags |= BS_FLAG_MXFP4_KV
         if n_labels:
             d.flags |= BS_FLAG_CLASSIFIER
             d.n_labels = n_labels
@@ -312,6 +317,7 @@ class Stage:
         self.hidden, self.vocab = hidden, vocab
         self.n_labels = n_labels
         self.kv_int8 = bool(kv_int8)
+        self.kv_mxfp4 = bool(kv_mxfp4)
         self.n_out = n_labels if n_labels else vocab  # logits per row of the last stage
         self.is_first, self.is_last = bool(d.is_first), bool(d.is_last)
         self.max_batch, self.max_ctx = max_batch, max_ctx

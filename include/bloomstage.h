@@ -119,6 +119,23 @@ typedef enum {
  *   bs_read_weights returns the dequantised values; bs_stage_info reports the real storage under weight_bytes.  The
  *   device layout is private to the library. */
 #define BS_FLAG_MXFP4_WEIGHTS 8
+/* desc->flags.  BS_FLAG_MXFP4_KV (bf16 stages; BS_ERR_INVALID on an fp32 stage or together with BS_FLAG_INT8_KV;
+ * head_dim a multiple of 32, else BS_ERR_UNSUPPORTED): the KV cache holds OCP MXFP4 along head_dim -- the
+ * BS_FLAG_MXFP4_WEIGHTS rule above, the block being 32 consecutive dims of one (position, head) K or V vector (ties
+ * to the even code, saturation at 6, amax < 2^-100 -> E = 127 and codes 0).  hd / 2 + hd / 32 bytes per vector: 68 B
+ * at hd = 128, against 132 B for BS_FLAG_INT8_KV and 256 B for bf16.  Orthogonal to BS_FLAG_INT8_WEIGHTS,
+ * BS_FLAG_MXFP4_WEIGHTS and BS_FLAG_CLASSIFIER.  Opt-in: round to nearest at 4 bits without calibration is lossy
+ * (about 11 % relative error per element).
+ *   Storage (private): codes [layer][K|V][slot][head][pos][hd / 2] bytes, then scales
+ *   [layer][K|V][slot][head][pos][hd / 32] E8M0 bytes, both zero at init and after bs_reset_kv; an all-zero record
+ *   dequantises to exactly 0.
+ *   Semantics, staging and its capacity error: BS_FLAG_INT8_KV's.  A dequantised value is exact in bf16, so a call
+ *   with seq > 1 (bf16 staging copy) and a call with seq == 1 (codes converted in registers) attend the same past.
+ *   Every call BS_FLAG_INT8_KV refuses (BS_STEP_VERIFY / VERIFY_DRAW, bs_forward_tree, bs_compact_kv,
+ *   bs_forward_ragged, bs_set_row_prefix) is refused here with the same status; bs_fork_kv / bs_copy_kv copy codes
+ *   and scales verbatim.  bs_read_kv returns the dequantised fp32 values; bs_stage_info reports
+ *   kv_bytes = layers * 2 * max_batch * n_head * max_ctx * (head_dim / 2 + head_dim / 32). */
+#define BS_FLAG_MXFP4_KV 16
 
 typedef struct bs_stage_desc {
   /* model (HF BloomConfig fields) */

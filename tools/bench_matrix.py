@@ -3,10 +3,11 @@
 Each row: one full model as one stage (the per-stage kernels are the same ones a pipeline stage
 runs), prefill `prompt` tokens, then time `steps` graph-replayed decode steps.  Reports tokens/s,
 ms/step and the stage's algorithmic HBM bytes/step (BASELINE.md formula) / step time.
-    python tools/bench_matrix.py [--quick] [--kv=int8 | --kv=bf16,int8 --reps=3] [--only=model:batch,...]
+    python tools/bench_matrix.py [--quick] [--kv=int8 | --kv=bf16,int8,mxfp4 --reps=3] [--only=model:batch,...]
                                  [--weights=bf16,int8,mxfp4]
 --kv=int8 builds the stage with the int8 KV cache (BS_FLAG_INT8_KV) and counts its bytes in algo_GB_per_step;
---kv=bf16,int8 alternates the two caches per configuration, --reps times each.
+--kv=mxfp4 the MXFP4 one (BS_FLAG_MXFP4_KV); --kv=bf16,int8,mxfp4 alternates the caches per configuration, --reps
+times each.
 --weights=bf16,int8,mxfp4 alternates the weight formats of the block matrices per configuration in the same way
 (BS_FLAG_INT8_WEIGHTS, BS_FLAG_MXFP4_WEIGHTS); algo_GB_per_step counts their bytes per weight.
 """
@@ -36,10 +37,10 @@ CONFIGS = [  # (model, batch, prompt, steps)
 MATRIX_BYTES = {"bf16": 2.0, "int8": 1.0, "mxfp4": config.MXFP4_BYTES_PER_WEIGHT}
 
 
-def run(name, B, P, K, W=4, kv_int8=False, weights="bf16"):
+def run(name, B, P, K, W=4, kv="bf16", weights="bf16"):
     m = config.get(name)
     st = Stage(m.hidden, m.n_head, m.n_layer, m.vocab, 0, m.n_layer, dtype="bf16", max_batch=B,
-               max_ctx=P + W + K + 1, max_tokens=max(B * P, B), seed=0, kv_int8=kv_int8,
+               max_ctx=P + W + K + 1, max_tokens=max(B * P, B), seed=0, kv_int8=kv == "int8", kv_mxfp4=kv == "mxfp4",
                int8_weights=weights == "int8", mxfp4_weights=weights == "mxfp4")
     cs = torch.cuda.Stream()
     with torch.cuda.stream(cs):
@@ -64,10 +65,10 @@ def run(name, B, P, K, W=4, kv_int8=False, weights="bf16"):
     st.close()
     ctx = P + W + K / 2
     byts = config.decode_step_bytes(m, m.n_layer, B, ctx, True, True,
-                                    kv_bytes=config.kv_bytes_per_element(m, kv_int8),
+                                    kv_bytes=config.kv_bytes_per_element(m, kv == "int8", kv_mxfp4=kv == "mxfp4"),
                                     matrix_bytes=MATRIX_BYTES[weights])
     ms = dt * 1e3 / K
-    return {"model": name, "weights": weights, "kv": "int8" if kv_int8 else "bf16", "batch": B, "prompt": P, "ctx_mid": ctx,
+    return {"model": name, "weights": weights, "kv": kv, "batch": B, "prompt": P, "ctx_mid": ctx,
             "tokens_per_s": B * K / dt, "ms_per_step": ms,
             "algo_GB_per_step": byts / 1e9, "hbm_GBps": byts / (ms * 1e-3) / 1e9,
             "hbm_frac": byts / (ms * 1e-3) / 1e9 / HBM_PEAK, "prefill_ms": tp * 1e3,
@@ -84,10 +85,10 @@ if __name__ == "__main__":
     if only:
         keep = {tuple(x.split(":")) for x in only[0].split(",")}
         cfgs = [c for c in cfgs if (c[0], str(c[1])) in keep]
-    # --kv=int8, or --kv=bf16,int8 --reps=3: the two caches alternate per configuration (an A/B inside one process)
+    # --kv=int8, or --kv=bf16,int8,mxfp4 --reps=3: the caches alternate per configuration (an A/B inside one process)
     kv = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--kv=")] or ["bf16"])[0].split(",")
-    if any(k not in ("bf16", "int8") for k in kv):
-        sys.exit(f"--kv takes bf16 and/or int8 (got {','.join(kv)})")
+    if any(k not in ("bf16", "int8", "mxfp4") for k in kv):
+        sys.exit(f"--kv takes bf16, int8 and/or mxfp4 (got {','.join(kv)})")
     wts = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--weights=")] or ["bf16"])[0].split(",")
     if any(w not in MATRIX_BYTES for w in wts):
         sys.exit(f"--weights takes bf16, int8 and/or mxfp4 (got {','.join(wts)})")
@@ -96,4 +97,4 @@ if __name__ == "__main__":
         for rep in range(reps):
             for k in kv:
                 for w in wts:
-                    print(json.dumps({**run(*c, kv_int8=k == "int8", weights=w), "rep": rep}), flush=True)
+                    print(json.dumps({**run(*c, kv=k, weights=w), "rep": rep}), flush=True)
